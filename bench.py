@@ -35,8 +35,6 @@ import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")    # before the HIP runtime starts: one hardware queue per trainer stream
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -107,6 +105,10 @@ def parse():
                          "epochs take ~4 s on the HIP train step (the reference's default is 1000) and fit the 50 clips")
     ap.add_argument("--sustain-seconds", type=float, default=5.0, help="length of the sustained leg (0 = skip)")
     ap.add_argument("--dis-metric", default="ours", choices=["ours", "mse", "cos"], help="match_loss metric of --method dc")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (the global loss and the trainer's learnable "
+                         "state, gathered over the ranks) as DIR/<name>.npy: float64 scalars, float32 arrays; an array above "
+                         "2**22 elements is written as a fixed seeded sample of its flattened values (same shape -> same positions)")
     return ap.parse_args()
 
 
@@ -462,6 +464,54 @@ def base_record(args, h, metric, dt, per_step, dtype, workload, parallelism, pre
             "data": "synthetic", "config": {"workload": workload, "precision": precision, "parallelism": parallelism}}
 
 
+DUMP_SAMPLE = 1 << 22          # elements written per array at most (16 MB of float32; four such arrays stay under 64 MB)
+
+
+def dump_outputs(args, h, loss, state):
+    """--dump-outputs: ``loss`` (the global loss of the last timed step) and ``state`` (name -> tensor: what the trainer hands
+    its caller after that step) as DIR/<name>.npy, on rank 0.  Every input of a run is seeded from the command line, so two
+    builds given the same arguments can be compared file for file.  -> summary for the JSON line, or None."""
+    if not args.dump_outputs or h.rank != 0:
+        return None
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    arrays = {"loss": np.asarray(float(loss), dtype=np.float64)}
+    for name, t in state.items():
+        arrays[name] = t.detach().float().cpu().numpy()
+    rec, nbytes = {}, 0
+    for name, a in arrays.items():
+        shape = list(a.shape)
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        nbytes += a.nbytes
+        assert nbytes <= 64 << 20, "--dump-outputs writes 64 MB at most"
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        rec[name] = {"shape": shape, "written": int(a.size)}
+    return {"dir": args.dump_outputs, "arrays": rec}
+
+
+def trainer_state(trainer, world):
+    """The learnable state a trainer holds after its latest step, whole (every rank calls: collectives where it is sharded by
+    class).  DM / DC: the synthetic clips; s2d: dynamic memories + hallucinator (the static memories are frozen); MTT: the
+    synthetic clips or memories + syn_lr (replicated over the ranks)."""
+    if hasattr(trainer, "sync"):
+        trainer.sync()
+    torch.cuda.synchronize()
+    if hasattr(trainer, "hal_w"):
+        dyn = trainer.dynamic
+        if world > 1 and hasattr(trainer, "c_lo"):          # S2DTrainer: every rank owns the dynamic rows of its classes
+            import torch.distributed as dist
+            parts = [None] * world
+            dist.all_gather_object(parts, dyn.cpu())
+            dyn = torch.cat(parts, 0)
+        state = {"dynamic": dyn, "hal_w": trainer.hal_w, "hal_b": trainer.hal_b}
+    else:
+        state = {"image_syn": trainer.gather_syn() if hasattr(trainer, "gather_syn") else trainer.image_syn}
+    if hasattr(trainer, "syn_lr"):
+        state["syn_lr"] = trainer.syn_lr
+    return state
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # DM / s2d (configs 1-3)
 # ------------------------------------------------------------------------------------------------------------------------
@@ -622,6 +672,7 @@ def bench_dm(args, h, distill, plan, geo, pool, backend, shard):
     def step(it):
         return gl(trainer.step(it, overlap=True))
     dt, per_step, prof, losses = h.run(step, trainer.sync, trainer.mark)
+    dumped = dump_outputs(args, h, losses[-1], trainer_state(trainer, world)) if args.dump_outputs else None
     # the evaluation runs on the synthetic clips as they are after EXACTLY warmup + steps iterations (before the sustained leg,
     # whose step count is set by the clock): DM steps are free of atomics, the evaluation's training steps run in the fixed-order
     # mode, so `eval.top1_per_seed` is the same in every run of the same command line
@@ -723,6 +774,8 @@ def bench_dm(args, h, distill, plan, geo, pool, backend, shard):
                                       "rows; a real batch is an index list, no per-step conversion") if backend.resident_rows else \
             "resident in HBM as fp32, converted per step"
         out["loss_last"] = float(losses[-1]) / args.classes
+        if dumped:
+            out["dump_outputs"] = dumped
         if getattr(trainer, "real_range", None) is not None:      # what the fp8-corrected last level's producer saw (distill.HipBackend.check_real_range)
             out["config"]["precision"]["real_last_level_activation_range"] = trainer.real_range
         out["step_tflops"] = step_flop / (dt / args.steps) / 1e12
@@ -831,6 +884,7 @@ def bench_dc(args, h, distill, geo, pool):
     def step(it):
         return trainer.global_loss(trainer.step(it))
     dt, per_step, _, losses = h.run(step, lambda: None, mark, profile=False)
+    dumped = dump_outputs(args, h, losses[-1], trainer_state(trainer, h.world)) if args.dump_outputs else None
     sustained = h.sustained(step, lambda: None, args.warmup + args.steps)
     # per-program times: under the class lanes every launch shares the GPU with seven others, so its event-to-event time is
     # not GPU time; one extra step on ONE lane (outside the timed region, on every rank: the step ends in a collective)
@@ -858,6 +912,8 @@ def bench_dc(args, h, distill, geo, pool):
                                                            args.frames, outer, inner),
                           "class-sharded x%d (owner-computes, no gradient exchange)" % world, networks.get_precision())
         out["loss_last"] = float(losses[-1]) / args.classes
+        if dumped:
+            out["dump_outputs"] = dumped
         out["step_tflops"] = step_flop / (dt / args.steps) / 1e12
         out["step_frac_of_mfma_peak"] = out["step_tflops"] / PEAK_TFLOPS
         roof = roofline_from_profile(prof1, device, {})
@@ -955,6 +1011,7 @@ def bench_mtt(args, h, distill, geo):
     def step(it):
         return tr.step(it, traj)
     dt, per_step, _, losses = h.run(step, lambda: None, mark, profile=False)
+    dumped = dump_outputs(args, h, losses[-1], trainer_state(tr, h.world)) if args.dump_outputs else None
     sustained = h.sustained(step, lambda: None, args.warmup + args.steps)
     prof = h.profile_steps(step, lambda: None, args.warmup + args.steps)
     topo = h.topology(len(range(rank, tr.batch_syn, max(world, 1))) * tr.syn_steps)      # this rank's share of every student batch
@@ -973,6 +1030,8 @@ def bench_mtt(args, h, distill, geo):
                           "student batch split x%d, all-reduce of flat gradient + Hessian-vector product per inner step" % world,
                           networks.get_precision())
         out["grand_loss_last"] = float(losses[-1])
+        if dumped:
+            out["dump_outputs"] = dumped
         out["syn_lr"] = float(tr.syn_lr)
         out["operand_format_of_the_twice_differentiable_passes"] = {
             "format": networks.get_precision()["match"],

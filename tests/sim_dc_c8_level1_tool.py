@@ -14,13 +14,14 @@ vd_c8_hi_byte: a_hi / 4 as e4m3).  Lives with the tests' tools: it imports the o
 
 usage: python tests/sim_dc_c8_level1_tool.py [real_clips=64] [seed=404] [levels=1]     (levels: "1", "0", "01": which levels run the variant)"""
 import math
+import os
 import sys
 import time
 
 import torch
 import torch.nn.functional as F
 
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import ref_cpu as R
 
 torch.set_num_threads(8)

@@ -2,8 +2,8 @@
 and group g multiplies by weights rounded up or down to neighbouring f16 values such that the mean over the groups equals
 the fp32 weight to 1/(2G) ulp.  Compares |mean over clips of (f(x; W_g(clip)) - f(x; W))| / |f| with plain rn16(W)
 (|mean d|) and with the value-pass remedy (|mean d - d_syn|).  Lives with the tests' tools: it imports the oracle."""
-import sys, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import ref_cpu as R
 torch.set_num_threads(8)
 

@@ -5,10 +5,11 @@ together.  Prints |mean_j (f_variant(x_j) - f(x_j))| / |mean_j f(x_j)| per sourc
 Used for DESIGN section 2 (the error budget of the shipped mixed mode).  Lives with the tests' tools: it imports the oracle.
 
 usage: python tests/sim_error_budget_tool.py [similar|independent] [nclips]"""
+import os
 import sys
 import torch
 import torch.nn.functional as F
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import ref_cpu as R
 from tests.sim_dither_tool import dither        # noqa: E402  (the dither rule of vd_pack_weights_dither, restated there)
 

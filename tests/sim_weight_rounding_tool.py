@@ -2,8 +2,8 @@
 its mean over a batch (the systematic part), and what is left after subtracting the synthetic clip's own perturbation
 (the value pass); plain rounding vs error-diffusion rounding along the taps / along K.  Lives with the tests' tools:
 it imports the oracle.  Output of the run recorded in DESIGN.md section 2."""
-import sys, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import ref_cpu as R
 torch.set_num_threads(8)
 torch.manual_seed(0)

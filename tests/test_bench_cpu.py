@@ -48,3 +48,30 @@ def test_an_n_rank_line_without_proof_of_its_ranks_has_no_value():
         assert why and word in why and line["value"] is None and line["value_median"] is None and line["refused"] == why
     # a gloo group on one device reports no RCCL rank count: the all-reduce of ones is the proof
     assert bench.refuse_unproven(dict(good, rccl={"note": "process group on gloo"}), 8) is None
+
+
+def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
+    """``--dump-outputs DIR``: the loss as a float64 scalar, every state array as float32; an array above 2**22 elements is a
+    seeded sample at the same positions in every run, and nothing but rank 0 writes."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)
+    state = {"image_syn": big.view(-1, 8), "syn_lr": torch.tensor(0.01)}
+    args = types.SimpleNamespace(dump_outputs=str(tmp_path / "a"))
+    rec = bench.dump_outputs(args, types.SimpleNamespace(rank=0), torch.tensor(3.5), state)
+    assert sorted(os.listdir(args.dump_outputs)) == ["image_syn.npy", "loss.npy", "syn_lr.npy"]
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float64 and float(loss) == 3.5
+    img = np.load(tmp_path / "a" / "image_syn.npy")
+    assert img.dtype == np.float32 and img.size == bench.DUMP_SAMPLE and np.all(np.diff(img) > 0)
+    assert rec["arrays"]["image_syn"] == {"shape": [(bench.DUMP_SAMPLE + 1000) // 8, 8], "written": bench.DUMP_SAMPLE}
+    assert np.load(tmp_path / "a" / "syn_lr.npy").dtype == np.float32
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(args.dump_outputs)) <= 64 << 20
+    args_b = types.SimpleNamespace(dump_outputs=str(tmp_path / "b"))
+    bench.dump_outputs(args_b, types.SimpleNamespace(rank=0), torch.tensor(3.5), state)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "image_syn.npy"), img)
+    assert bench.dump_outputs(types.SimpleNamespace(dump_outputs=str(tmp_path / "c")), types.SimpleNamespace(rank=1),
+                              torch.tensor(3.5), state) is None
+    assert not os.path.exists(tmp_path / "c")

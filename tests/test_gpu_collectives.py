@@ -28,13 +28,32 @@ def _free_port():
         return str(s.getsockname()[1])
 
 
+GPU_PROCS = 5       # child processes at one time (ranks and their launchers): with this test process, at most six on the card
+
+
 def _together(*jobs):
     """Run the child benchmarks of one test CONCURRENTLY (round 6: these are logic runs of 2 - 3 tiny steps whose time is process
     start-up -- import, planning, engine construction -- and the children share the one GPU without touching each other's
-    results; serially the file took 195 s of the driver's suite).  -> the jobs' results, in order."""
+    results; serially the file took 195 s of the driver's suite).  A job is a callable (one process) or a (callable, processes)
+    pair -- a two-rank job is three: the ranks and the process that launched them; jobs start while their processes fit in
+    GPU_PROCS.  -> the jobs' results, in order."""
+    import threading
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(6, len(jobs))) as ex:
-        futs = [ex.submit(j) for j in jobs]
+    free, cv = [GPU_PROCS], threading.Condition()
+
+    def run(job):
+        fn, n = job if isinstance(job, tuple) else (job, 1)
+        with cv:
+            cv.wait_for(lambda: free[0] >= n)
+            free[0] -= n
+        try:
+            return fn()
+        finally:
+            with cv:
+                free[0] += n
+                cv.notify_all()
+    with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
+        futs = [ex.submit(run, j) for j in jobs]
         return [f.result() for f in futs]
 
 
@@ -105,12 +124,12 @@ def test_two_ranks_share_the_gpu_over_gloo_and_match_one_rank():
     dc = ["--method", "dc", "--classes", "3", "--ipc", "1", "--frames", "8", "--size", "64", "--batch-real", "8", "--pool-per-class", "12"]
     mtt = ["--method", "mtt", "--classes", "8", "--frames", "8", "--size", "64", "--syn-steps", "2", "--batch-syn", "8"]
     shards = [(k, sh, per) for k, (sh, per) in enumerate((("class", 1), ("batch", 2), ("hybrid", 2)))
-              if sh != "hybrid" or os.environ.get("VD_TEST_ALL_SHARDS") == "1"]      # (the eight-rank test below runs the hybrid decomposition)
+              if sh != "hybrid" or os.environ.get("VD_TEST_ALL_SHARDS") == "1"]      # (the four-rank test below runs the hybrid decomposition)
     # every child of this test at once: four one-rank references and the two-rank runs (a fixed rendezvous port each)
     one, s2d_a, dc_a, mtt_a, s2d_b, dc_b, mtt_b, *two_runs = _together(
         lambda: _bench(small + ["--shard", "class"]), lambda: _bench(s2d), lambda: _bench(dc), lambda: _bench(mtt),
-        lambda: two(s2d, 29555), lambda: two(dc, 29556), lambda: two(mtt, 29557),
-        *[lambda k=k, sh=sh: two(small + ["--shard", sh], 29551 + k) for k, sh, _ in shards])
+        (lambda: two(s2d, 29555), 3), (lambda: two(dc, 29556), 3), (lambda: two(mtt, 29557), 3),
+        *[(lambda k=k, sh=sh: two(small + ["--shard", sh], 29551 + k), 3) for k, sh, _ in shards])
     for (k, shard, per_step), got in zip(shards, two_runs):
         c = got["collectives"]
         assert got["n_gpus"] == 2 and c["backend"] == "gloo" and not c["forced_on_one_rank"]
@@ -162,7 +181,7 @@ def test_pixel_gradient_allreduce_leg():
         lambda: _bench(small, dict(FORCE, VD_BENCH_EXCHANGE_LEG="1", MASTER_PORT="29543")),
         lambda: _bench(small + long, dict(FORCE, VD_BENCH_EXCHANGE_LEG="1", MASTER_PORT="29545")),
         lambda: _bench(small + long + ["--exchange", "allreduce"], dict(FORCE, VD_BENCH_EXCHANGE_LEG="1", MASTER_PORT="29544")),
-        spawned_two)
+        (spawned_two, 3))
     leg = one["exchange_allreduce"]
     assert leg["through"].startswith("vd_comm_allreduce_f32") and leg["allreduce_calls"] == 5
     assert leg["pixel_gradient_bytes_per_step"] == 6 * 16 * 3 * 112 * 112 * 4 and leg["allreduce_ms_mean"] > 0
@@ -185,25 +204,26 @@ def test_pixel_gradient_allreduce_leg():
     assert abs(two["loss_last"] / one["loss_last"] - 1) < 1e-4
 
 
-def test_eight_ranks_share_the_gpu_with_the_default_decomposition():
-    """``bench.py --gpus 8`` with NO launcher in front (the shape of the driver's one-GPU command; bench.py spawns the ranks;
-    the launcher form is exercised by the two-rank test above), eight processes, default --shard auto ->
-    the hybrid decomposition: 6 whole classes per rank + the real batches of classes 48 and 49 split eight ways), all ranks on
-    device 0 over gloo: the all-reduced DM loss equals the one-rank loss, rank 0 evaluates the gathered 50 synthetic clips."""
+def test_four_ranks_share_the_gpu_with_the_default_decomposition():
+    """``bench.py --gpus 4`` with NO launcher in front (the shape of the driver's command; bench.py spawns the ranks; the launcher
+    form is exercised by the two-rank test above), four ranks (with their parent and this process, six on the card), default --shard
+    auto on 18 classes -> the hybrid decomposition: 4 whole classes per rank + the real batches of classes 16 and 17 split four
+    ways), all ranks on device 0 over gloo: the all-reduced DM loss equals the one-rank loss, rank 0 evaluates the gathered 18
+    synthetic clips."""
     e = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VD_BENCH_ONE_DEVICE="1")
     e.pop("WORLD_SIZE", None); e.pop("RANK", None)
     args = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sustain-seconds", "0", "--no-extra-legs", "--eval-epochs", "1",
-            "--eval-seeds", "1"]
-    # NO launcher in front: bench.py starts its eight ranks itself (spawn_ranks) and relays rank 0's line
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "8"] + args, cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)
+            "--eval-seeds", "1", "--classes", "18"]
+    # NO launcher in front: bench.py starts its four ranks itself (spawn_ranks) and relays rank 0's line
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "4"] + args, cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line on stdout"
     got = json.loads(lines[-1])
     one = _bench(args)
-    assert got["n_gpus"] == 8 and got["config"]["parallelism"].startswith("hybrid x8") and one["n_gpus"] == 1
-    assert got["ranks_seen"] == 8 and got["launched_by"] == "bench.py spawn_ranks" and one["ranks_seen"] == 1
-    assert got["clips_per_step"] == [400] * 8 and one["clips_per_step"] == [3200]          # 6 whole classes + 1/8 of two = 400 per rank
+    assert got["n_gpus"] == 4 and got["config"]["parallelism"].startswith("hybrid x4") and one["n_gpus"] == 1
+    assert got["ranks_seen"] == 4 and got["launched_by"] == "bench.py spawn_ranks" and one["ranks_seen"] == 1
+    assert got["clips_per_step"] == [288] * 4 and one["clips_per_step"] == [1152]          # 4 whole classes + 1/4 of two = 288 per rank
     c = got["collectives"]
     assert c["backend"] == "gloo" and c["all_reduce"] == 3 * 2 and c["all_gather"] == 1, c      # per step: split-class feature sums + loss
     assert abs(got["loss_last"] / one["loss_last"] - 1) < 1e-5, (got["loss_last"], one["loss_last"])
