@@ -508,6 +508,26 @@ int vd_comm_allreduce_f32(VdComm* c, const float* send, float* recv, int64_t n, 
 int vd_comm_allgather_f32(VdComm* c, const float* send, float* recv, int64_t n_per_rank, void* stream);
 void vd_comm_free(VdComm* c);
 
+/* Coreset selection (distill_coreset.py:72-105: the herding and k-center branches after `features = embed(imgs)`).
+ * feats: fp32 rows of `dim` features; class c owns rows offsets[c] .. offsets[c] + counts[c] - 1 (offsets int64, counts int32,
+ * both DEVICE arrays of nclass entries, every count <= max_count).  Picks, in selection order, land in
+ * out_idx[c * ipc .. c * ipc + ipc - 1] as row indices into feats; a class with fewer than ipc rows gets -1 for all of its picks
+ * and leaves the others unaffected.  Both criteria run on the class's centred Gram matrix in fp64 (mean in fp64, product on
+ * v_mfma_f64_16x16x4_f64), ties to the lowest index:
+ *   VD_CORESET_HERDING: argmin over unchosen j of ||(i+1) m - sum_chosen f - f_j|| (the reference's herding, exactly);
+ *   VD_CORESET_KCENTER: greedy farthest point -- first the clip closest to the mean, then argmax over unchosen j of the
+ *                       distance to the nearest chosen clip (the algorithm the reference's k-center branch intends).
+ * workspace: vd_coreset_workspace_bytes(nclass, max_count) bytes (nclass x max_count^2 fp64 Gram blocks).  Two launches on
+ * `stream`, no host synchronisation.  -2: dim outside 1..VD_CORESET_MAX_DIM, max_count outside 1..VD_CORESET_MAX_COUNT,
+ * ipc < 1, an unknown method or a short workspace. */
+#define VD_CORESET_HERDING   0
+#define VD_CORESET_KCENTER   1
+#define VD_CORESET_MAX_COUNT 4096
+#define VD_CORESET_MAX_DIM   8192
+int64_t vd_coreset_workspace_bytes(int nclass, int max_count);
+int vd_coreset_select(const float* feats, int dim, const int64_t* offsets, const int32_t* counts, int nclass, int max_count,
+                      int ipc, int method, int64_t* out_idx, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
