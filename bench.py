@@ -2,6 +2,7 @@
 """Headline benchmark: distillation steps/s on N MI355X, for the five BASELINE.json configurations.
 
     python bench.py                                   # config 2: DM, miniUCF101 shape, IPC=1, 112x112x16 (the headline)
+    python bench.py --full                            # the same + CPU baseline, eval, sustained and extra legs, measured peak
     python bench.py --method s2d                      # config 3: DM + static/dynamic memories
     python bench.py --method dc  --classes 51 --ipc 5                       # config 4: gradient matching
     python bench.py --method mtt --classes 400 --frames 8 --size 64         # config 5: MTT + static/dynamic memories
@@ -15,19 +16,23 @@ ships): randn clips standardised per channel, generated on the device; inputs re
 
 Rank 0 prints ONE JSON line (contract in the task description).  `value` = steps / wall time of the timed region
 (barrier + synchronize on both sides, max over ranks); `ms_per_step_median` is the median of the per-step intervals
-between HIP events recorded behind each step's last kernel.  Extra objects:
-  roofline      -- the conv tile program with the largest share of the timed region's GPU time: algorithmic FLOP per launch
-                   / mean launch time (HIP events on the launch stream, inside the timed region) against the 2.5 PFLOP/s
-                   dense 16-bit MFMA peak; `peak_measured` = this box's MFMA-saturating microbenchmark (vd_mfma_peak);
-                   `traffic` = HBM bytes per launch from the committed PMC passes, quoted only while the file's stamp equals the
-                   hash of this checkout's kernel sources (else null; see traffic_source);
+between HIP events recorded behind each step's last kernel.  A plain run does only what that line needs: set-up, warm-up,
+the timed steps, --dump-outputs, and the figures taken from the timed region itself.  Extra objects:
+  roofline      -- DM / s2d: the conv tile program with the largest share of the timed region's GPU time: algorithmic FLOP per
+                   launch / mean launch time (HIP events on the launch stream, inside the timed region) against the 2.5 PFLOP/s
+                   dense 16-bit MFMA peak; `traffic` = HBM bytes per launch from the committed PMC passes, quoted only while the
+                   file's stamp equals the hash of this checkout's kernel sources (else null; see traffic_source);
   per_rank      -- every rank's real clips, own ms per step, wait at the closing barrier, real-side ms, exchange ms (N > 1:
-                   what tells an unbalanced partition from a slow collective from a slow device);
+                   what tells an unbalanced partition from a slow collective from a slow device).
+With --full, whatever takes runs of its own after the timed region as well:
+  roofline      -- `peak_measured` = this box's MFMA-saturating microbenchmark (vd_mfma_peak); DM: `alone` = the real side
+                   launched with nothing else on the chip; DC / MTT: the whole object, from one extra profiled step;
   cpu_baseline  -- the CPU oracle (torch fp32 ops == what the reference runs on a CPU) timed on this host's cores on a
                    bounded sample of the same workload, extrapolated to steps/s; rank 0, N=1 only;
   eval          -- evaluate_synset on the synthetic clips (HIP train step + HIP inference): a reproducible SMOKE of that path, not
                    an accuracy metric (accuracy parity: fixture G16, tests/test_gpu_eval_parity.py);
-  sustained     -- the same step loop run for --sustain-seconds: steps/s once clocks have settled.
+  sustained     -- the same step loop run for --sustain-seconds: steps/s once clocks have settled;
+  parity_mode, fast_mode, exchange_*  -- DM: short timed legs of the same workload in other precision / exchange modes.
 """
 import argparse
 import json
@@ -64,7 +69,7 @@ def parse():
                     help="real side's last conv level: x3 = hi+lo operand pairs (default, VD_REAL_LAST), c8 = hi+lo with the two correction "
                          "products on the fp8 matrix instruction (two MFMA-equivalents per product), x1 = single pass like the others")
     ap.add_argument("--chunk", type=int, default=3200, help="real clips per launch (all of a single-GPU step by default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-classes", type=int, default=10, help="dm/s2d: class terms timed for the CPU baseline")
     ap.add_argument("--shard", default="auto", choices=["auto", "class", "batch", "hybrid"],
                     help="multi-GPU decomposition of dm: whole classes per rank (uneven blocks, no data-path collective); 1/N of every "
@@ -76,7 +81,7 @@ def parse():
                          "nothing crosses xGMI) or allreduce (the task's literal 'all-reduce of the matching-loss gradient': the full "
                          "C*ipc-clip gradient tensor, 120 MB at config 2, summed over the ranks through vd_comm_allreduce_f32 = RCCL).  "
                          "With more than one rank the mode that is NOT timed runs as a short extra leg (exchange_allreduce / exchange_owner)")
-    ap.add_argument("--exchange-leg", action="store_true", help="dm: run the other exchange mode's short leg even with --no-extra-legs")
+    ap.add_argument("--exchange-leg", action="store_true", help="dm, --full: run the other exchange mode's short leg even with --no-extra-legs")
     ap.add_argument("--vd-comm", choices=["auto", "on", "off"], default="auto",
                     help="the library's own RCCL communicator (hip.Comm -> vd_comm_*) for the pixel-gradient all-reduce and the `rccl` "
                          "block of the line.  auto: on one rank (where it has been exercised on every GPU test run), OFF on more than "
@@ -93,22 +98,27 @@ def parse():
                          "(SURVEY 8(d); top-1 is chance by construction).  Same value statistics, same timings.")
     ap.add_argument("--pool-noise", type=float, default=1.5, help="--pool-kind templates: noise amplitude next to the template (rms 0.67)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="dm: skip the two short extra timed legs (parity_mode = all hi+lo pairs, fast_mode = round 2's single-pass mode)")
+                    help="dm, --full: skip the two short extra timed legs (parity_mode = all hi+lo pairs, fast_mode = round 2's single-pass mode)")
     ap.add_argument("--seed", type=int, default=0, help="seed of torch's global generators (dropout masks of DC / MTT, loader shuffles)")
-    ap.add_argument("--no-alone", action="store_true", help="dm: skip the stand-alone launches of the real side after the timed region "
+    ap.add_argument("--no-alone", action="store_true", help="dm, --full: skip the stand-alone launches of the real side after the timed region "
                     "(roofline.alone); profiling runs use it so that the kernel statistics hold in-step launches only")
     ap.add_argument("--eval-atomic", action="store_true", help="dm: run the eval leg's training steps in the default (fp32-atomic) accumulation "
                     "mode instead of the fixed-order one (then top1_per_seed moves in its last digits from run to run)")
     ap.add_argument("--eval-seeds", type=int, default=5, help="dm: networks (fixed seeds) the eval leg trains; top1 is their mean")
     ap.add_argument("--eval-epochs", type=int, default=500,
-                    help="dm: after the timed steps run evaluate_synset on the synthetic clips for this many epochs (0 = skip); 500 "
+                    help="dm, --full: after the timed steps run evaluate_synset on the synthetic clips for this many epochs (0 = skip); 500 "
                          "epochs take ~4 s on the HIP train step (the reference's default is 1000) and fit the 50 clips")
-    ap.add_argument("--sustain-seconds", type=float, default=5.0, help="length of the sustained leg (0 = skip)")
+    ap.add_argument("--sustain-seconds", type=float, default=5.0, help="--full: length of the sustained leg (0 = skip)")
     ap.add_argument("--dis-metric", default="ours", choices=["ours", "mse", "cos"], help="match_loss metric of --method dc")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps write what the last timed step computed (the global loss and the trainer's learnable "
                          "state, gathered over the ranks) as DIR/<name>.npy: float64 scalars, float32 arrays; an array above "
                          "2**22 elements is written as a fixed seeded sample of its flattened values (same shape -> same positions)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the CPU baseline, the eval and sustained legs, "
+                         "dm's extra precision and exchange legs, the measured MFMA peak, the stand-alone real side and DC / MTT's "
+                         "profiling step (the --no-* switches above then skip single legs).  Without it a run sets up, warms up, "
+                         "times the steps, dumps its outputs and prints the line")
     return ap.parse_args()
 
 
@@ -677,13 +687,13 @@ def bench_dm(args, h, distill, plan, geo, pool, backend, shard):
     # whose step count is set by the clock): DM steps are free of atomics, the evaluation's training steps run in the fixed-order
     # mode, so `eval.top1_per_seed` is the same in every run of the same command line
     ev = None
-    if args.eval_epochs > 0 and not s2d:
+    if args.full and args.eval_epochs > 0 and not s2d:
         ev = run_eval(args, trainer, pool, device, rank)
-    sustained = h.sustained(step, trainer.sync, args.warmup + args.steps)
+    sustained = h.sustained(step, trainer.sync, args.warmup + args.steps) if args.full else None
     # Two short extra legs of the same workload, on record next to the headline: the fp32-grade mode (every operand a hi+lo pair)
     # and round 2's fast mode (single pass on every real level and in the input gradient).  Every rank runs them.
     legs = {}
-    if not s2d and not args.no_extra_legs:
+    if args.full and not s2d and not args.no_extra_legs:
         from video_distillation_amd.networks import _batch_hint
         for name, kw in (("parity_mode", dict(prec_real=args.prec_syn, prec_syn=args.prec_syn, prec_bwd=args.prec_syn)),
                          ("fast_mode", dict(prec_real=args.prec_real, prec_syn=args.prec_syn, prec_bwd=args.prec_real, real_last="x1"))):
@@ -714,7 +724,7 @@ def bench_dm(args, h, distill, plan, geo, pool, backend, shard):
     # The exchange mode that is NOT the timed one, as a short leg of the same workload in the shipped precision mode: with
     # --exchange owner (default) this is the literal pixel-gradient all-reduce, so that its cost stands next to owner-computes
     # the first time more than one GPU is available.  Every rank runs it (it contains the collective).
-    if not s2d and (world > 1 or os.environ.get("VD_BENCH_EXCHANGE_LEG") == "1") and (args.exchange_leg or not args.no_extra_legs):
+    if args.full and not s2d and (world > 1 or os.environ.get("VD_BENCH_EXCHANGE_LEG") == "1") and (args.exchange_leg or not args.no_extra_legs):
         other = "allreduce" if args.exchange == "owner" else "owner"
         tr3 = distill.DMTrainer(backend, pool, args.classes, args.ipc, args.batch_real, lr_img=1.0, momentum=0.5, rank=rank, world=world,
                                 shard=shard, exchange=other, comm=h.open_comm() if other == "allreduce" else None)
@@ -786,9 +796,10 @@ def bench_dm(args, h, distill, plan, geo, pool, backend, shard):
         if roof:
             clips = roof["flop_per_launch"] / (2.0 * macs[1]) if "fwd1" in roof["kernel"] else None
             roof["traffic"], roof["traffic_source"] = pmc_traffic("conv1_fwd_f16", clips) if clips else (None, None)
-            roof["peak_measured"] = mfma_peak(device)
-            roof["frac_of_measured"] = roof["achieved"] / roof["peak_measured"]
-            if not s2d and world == 1 and not args.no_alone:
+            if args.full:
+                roof["peak_measured"] = mfma_peak(device)
+                roof["frac_of_measured"] = roof["achieved"] / roof["peak_measured"]
+            if args.full and not s2d and world == 1 and not args.no_alone:
                 roof["alone"] = real_side_alone(trainer, backend, args, macs, args.warmup + args.steps + 8)
             for p in roof["programs"]:
                 if p["program"] in ("fwd0", "fwd2") and p["operands"] == args.prec_real:
@@ -807,7 +818,7 @@ def bench_dm(args, h, distill, plan, geo, pool, backend, shard):
         out.update(topo)
         out["per_rank"] = per_rank
         out["exchange"] = dict({"mode": args.exchange}, **(exchange_record(trainer, args, geo, h) if not s2d else {}))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_dm(args, trainer, backend, args.warmup + args.steps, s2d if s2d else None)
     finish(h, out)
 
@@ -885,19 +896,21 @@ def bench_dc(args, h, distill, geo, pool):
         return trainer.global_loss(trainer.step(it))
     dt, per_step, _, losses = h.run(step, lambda: None, mark, profile=False)
     dumped = dump_outputs(args, h, losses[-1], trainer_state(trainer, h.world)) if args.dump_outputs else None
-    sustained = h.sustained(step, lambda: None, args.warmup + args.steps)
+    sustained = h.sustained(step, lambda: None, args.warmup + args.steps) if args.full else None
     # per-program times: under the class lanes every launch shares the GPU with seven others, so its event-to-event time is
     # not GPU time; one extra step on ONE lane (outside the timed region, on every rank: the step ends in a collective)
     # attributes the conv time to the programs
-    lanes_env = os.environ.get("VD_GM_LANES")
-    os.environ["VD_GM_LANES"] = "1"
-    try:
-        prof1 = h.profile_steps(step, lambda: None, args.warmup + args.steps)
-    finally:
-        if lanes_env is None:
-            del os.environ["VD_GM_LANES"]
-        else:
-            os.environ["VD_GM_LANES"] = lanes_env
+    prof1 = []
+    if args.full:
+        lanes_env = os.environ.get("VD_GM_LANES")
+        os.environ["VD_GM_LANES"] = "1"
+        try:
+            prof1 = h.profile_steps(step, lambda: None, args.warmup + args.steps)
+        finally:
+            if lanes_env is None:
+                del os.environ["VD_GM_LANES"]
+            else:
+                os.environ["VD_GM_LANES"] = lanes_env
     topo = h.topology(args.batch_real * len(trainer.classes))
     out = None
     if rank == 0:
@@ -925,7 +938,7 @@ def bench_dc(args, h, distill, geo, pool):
         if sustained:
             out["sustained"] = sustained
         out.update(topo)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_dc(args, trainer, geo, args.warmup + args.steps + 1)
     finish(h, out)
 
@@ -1012,8 +1025,8 @@ def bench_mtt(args, h, distill, geo):
         return tr.step(it, traj)
     dt, per_step, _, losses = h.run(step, lambda: None, mark, profile=False)
     dumped = dump_outputs(args, h, losses[-1], trainer_state(tr, h.world)) if args.dump_outputs else None
-    sustained = h.sustained(step, lambda: None, args.warmup + args.steps)
-    prof = h.profile_steps(step, lambda: None, args.warmup + args.steps)
+    sustained = h.sustained(step, lambda: None, args.warmup + args.steps) if args.full else None
+    prof = h.profile_steps(step, lambda: None, args.warmup + args.steps) if args.full else []
     topo = h.topology(len(range(rank, tr.batch_syn, max(world, 1))) * tr.syn_steps)      # this rank's share of every student batch
     out = None
     if rank == 0:
@@ -1050,7 +1063,7 @@ def bench_mtt(args, h, distill, geo):
         if sustained:
             out["sustained"] = sustained
         out.update(topo)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_mtt(args, tr, traj, C, s2d)
     finish(h, out)
 

@@ -75,3 +75,14 @@ def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
     assert bench.dump_outputs(types.SimpleNamespace(dump_outputs=str(tmp_path / "c")), types.SimpleNamespace(rank=1),
                               torch.tensor(3.5), state) is None
     assert not os.path.exists(tmp_path / "c")
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """A plain ``bench.py`` run times its steps and prints the line; the legs that take runs of their own need ``--full``."""
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "1"])
+    args = bench.parse()
+    assert not args.full and args.steps == 5 and args.warmup == 1
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    args = bench.parse()
+    assert args.full and args.no_cpu_baseline

@@ -503,6 +503,45 @@ def test_two_gpu_bench_matches_single_gpu_loss():
         assert abs(two["loss_last"] / one["loss_last"] - 1) < 1e-4, (shard, two["loss_last"], one["loss_last"])
 
 
+def test_plain_bench_runs_only_what_the_headline_needs():
+    """`bench.py` without --full: the headline line from the timed steps and nothing that takes runs of its own (CPU baseline,
+    eval, sustained and extra legs, measured MFMA peak, stand-alone real side, DC's profiling step); with --full those come
+    back, and the timed steps are the same steps either way."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dm = ["--steps", "2", "--warmup", "1", "--classes", "4", "--pool-per-class", "70"]
+    dc = ["--steps", "2", "--warmup", "1", "--method", "dc", "--classes", "3", "--ipc", "1", "--frames", "8", "--size", "64",
+          "--batch-real", "8", "--pool-per-class", "12"]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+
+    def run(extra, **more):
+        out = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + extra, cwd=root, env=dict(env, **more), capture_output=True,
+                             text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, "exactly one JSON line on stdout"
+        return json.loads(lines[0])
+    extras = ("cpu_baseline", "eval", "sustained", "parity_mode", "fast_mode", "exchange_allreduce")
+    plain = run(dm)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert plain[key] is not None, key
+    assert plain["unit"] == "steps/s" and plain["higher_is_better"] and plain["steps"] == 2 and plain["warmup"] == 1
+    assert abs(plain["value"] * plain["ms_per_step"] / 1e3 - 1) < 1e-9
+    assert not [k for k in extras if k in plain], plain.keys()
+    roof = plain["roofline"]                     # taken from the timed steps' own launches: stays
+    assert roof["launches"] > 0 and "traffic" in roof and "peak_measured" not in roof and "alone" not in roof
+    full = run(dm + ["--full", "--eval-epochs", "1", "--eval-seeds", "1", "--sustain-seconds", "0.1", "--cpu-classes", "1"])
+    assert all(k in full for k in ("cpu_baseline", "eval", "sustained", "parity_mode", "fast_mode"))
+    assert full["roofline"]["peak_measured"] > 0 and "alone" in full["roofline"]
+    assert abs(full["loss_last"] / plain["loss_last"] - 1) < 1e-6
+    plain = run(dc, VD_DETERMINISTIC="1")          # (fixed summation order: the dropout masks are seeded, the atomics' order is not)
+    assert plain["value"] > 0 and not [k for k in extras + ("roofline",) if k in plain], plain.keys()
+    full = run(dc + ["--full", "--no-cpu-baseline", "--sustain-seconds", "0"], VD_DETERMINISTIC="1")
+    assert full["roofline"]["launches"] > 0 and abs(full["loss_last"] / plain["loss_last"] - 1) < 1e-4
+
+
 def test_match_loss_trailing_unit_axis_rows_and_many_tensors():
     """'ours' on a 5-D tensor whose last axis is 1 (the (K,128,1,1,1) logit-conv gradient): every element is its own
     cosine row, 0 or 2 by sign (utils.py:649-651 fall-through) -- not a flat sum; and a list longer than one launch's 16

@@ -17,7 +17,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sustain-seconds", "0", "--no-extra-legs"]
+# --full: the collectives counted below include the eval leg's all-gather, DC / MTT's profiling step and the exchange leg
+COMMON = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--sustain-seconds", "0", "--no-extra-legs"]
 FORCE = {"VD_BENCH_FORCE_DIST": "1", "VD_FORCE_COLLECTIVES": "1", "VD_FORCE_BATCH_SHARD": "1", "MASTER_PORT": "29541"}
 
 
@@ -212,7 +213,7 @@ def test_four_ranks_share_the_gpu_with_the_default_decomposition():
     synthetic clips."""
     e = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VD_BENCH_ONE_DEVICE="1")
     e.pop("WORLD_SIZE", None); e.pop("RANK", None)
-    args = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sustain-seconds", "0", "--no-extra-legs", "--eval-epochs", "1",
+    args = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--sustain-seconds", "0", "--no-extra-legs", "--eval-epochs", "1",
             "--eval-seeds", "1", "--classes", "18"]
     # NO launcher in front: bench.py starts its four ranks itself (spawn_ranks) and relays rank 0's line
     out = subprocess.run([sys.executable, "bench.py", "--gpus", "4"] + args, cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)

@@ -11,15 +11,15 @@ PART=${PART:-12}
 export TMPDIR=/tmp
 if [[ $PART == *1* ]]; then
 rm -rf $OUT; mkdir -p $OUT
-python3 bench.py --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/bench_1gpu.json
-python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs --sustain-seconds 0 2>/dev/null | tail -1 > $OUT/bench_1gpu_again.json
-python3 bench.py --method s2d --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/bench_s2d.json
-python3 bench.py --frames 8 --size 64 --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/bench_config1_shape.json
-python3 bench.py --method dc --classes 51 --ipc 5 --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_dc.json
-python3 bench.py --method mtt --classes 400 --frames 8 --size 64 --steps 5 --warmup 2 2>/dev/null | tail -1 > $OUT/bench_mtt.json
-VD_PREC_MATCH=bf16x3 python3 bench.py --method mtt --classes 400 --frames 8 --size 64 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_mtt_bf16x3.json
-VD_PREC_MATCH=bf16x3 python3 bench.py --method dc --classes 51 --ipc 5 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_dc_bf16x3.json
-VD_BENCH_ONE_DEVICE=1 python3 bench.py --gpus 8 --steps 3 --warmup 1 --no-cpu-baseline --sustain-seconds 0 --eval-epochs 1 --eval-seeds 1 --exchange-leg --no-extra-legs 2>/dev/null | tail -1 > $OUT/bench_8ranks_one_device.json
+python3 bench.py --full --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/bench_1gpu.json
+python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs --sustain-seconds 0 2>/dev/null | tail -1 > $OUT/bench_1gpu_again.json
+python3 bench.py --full --method s2d --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/bench_s2d.json
+python3 bench.py --full --frames 8 --size 64 --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/bench_config1_shape.json
+python3 bench.py --full --method dc --classes 51 --ipc 5 --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_dc.json
+python3 bench.py --full --method mtt --classes 400 --frames 8 --size 64 --steps 5 --warmup 2 2>/dev/null | tail -1 > $OUT/bench_mtt.json
+VD_PREC_MATCH=bf16x3 python3 bench.py --full --method mtt --classes 400 --frames 8 --size 64 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_mtt_bf16x3.json
+VD_PREC_MATCH=bf16x3 python3 bench.py --full --method dc --classes 51 --ipc 5 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_dc_bf16x3.json
+VD_BENCH_ONE_DEVICE=1 python3 bench.py --full --gpus 8 --steps 3 --warmup 1 --no-cpu-baseline --sustain-seconds 0 --eval-epochs 1 --eval-seeds 1 --exchange-leg --no-extra-legs 2>/dev/null | tail -1 > $OUT/bench_8ranks_one_device.json
 python3 tools/mfma_peak.py > $OUT/mfma_peak.txt 2>/dev/null
 python3 tools/l0_ab.py 3200 8 > $OUT/l0_kernel_ab.txt 2>/dev/null
 python3 tools/stamps_l0.py 3200 5 2>/dev/null | tail -10 > $OUT/l0_phase_stamps.txt
@@ -38,12 +38,12 @@ prof() {  # name, then the program and its arguments
   timeout -k 5 280 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -- "$@" > $OUT/$name.log 2>&1
   cp $(ls $OUT/$name/*/*kernel_stats.csv | head -1) $OUT/${name}_kernel_stats.csv
 }
-prof bench python3 $ROOT/bench.py --steps 8 --warmup 2 --no-cpu-baseline --eval-epochs 0 --sustain-seconds 0 --no-extra-legs --no-alone
+prof bench python3 $ROOT/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --eval-epochs 0 --sustain-seconds 0 --no-extra-legs --no-alone
 grep '"metric"' $OUT/bench.log | tail -1 > $OUT/bench_1gpu_under_rocprof.json
 cp $(ls $OUT/bench/*/*kernel_trace.csv | head -1) $OUT/bench_kernel_trace.csv
-prof s2d python3 $ROOT/bench.py --method s2d --steps 8 --warmup 2 --no-cpu-baseline --sustain-seconds 0
-prof dc python3 $ROOT/bench.py --method dc --classes 8 --ipc 5 --steps 2 --warmup 1 --no-cpu-baseline --sustain-seconds 0
-prof mtt python3 $ROOT/bench.py --method mtt --classes 400 --frames 8 --size 64 --steps 2 --warmup 1 --no-cpu-baseline --sustain-seconds 0
+prof s2d python3 $ROOT/bench.py --full --method s2d --steps 8 --warmup 2 --no-cpu-baseline --sustain-seconds 0
+prof dc python3 $ROOT/bench.py --full --method dc --classes 8 --ipc 5 --steps 2 --warmup 1 --no-cpu-baseline --sustain-seconds 0
+prof mtt python3 $ROOT/bench.py --full --method mtt --classes 400 --frames 8 --size 64 --steps 2 --warmup 1 --no-cpu-baseline --sustain-seconds 0
 prof aux python3 $ROOT/tools/bench_aux.py
 prof syn_side python3 $ROOT/tools/syn_side_trace.py 20
 prof train_atomic python3 $ROOT/tools/train_trace.py 50
