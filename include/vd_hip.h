@@ -438,6 +438,22 @@ int vd_replica_sum(float* rep, int replicas, int rows, int cols, float* out, voi
 int vd_frames_normalize(const void* src_u8, float* dst, int64_t nframes, int height, int width, const float* mean3,
                         const float* std3, void* stream);
 
+/* Clips drawn per read out of a device-resident store of whole videos (replaces the 16 JPEG decodes + flip + resize / crop +
+ * ToTensor + Normalize of every `__getitem__` of the reference's frame-folder datasets, distill_utils/dataset.py:201-249 and
+ * its twins :301-351, :420-467, :519-568, and with them the host side of the three test passes of utils.py:793-824):
+ * frames_u8 (store_frames, src_h, src_w, 3) uint8 holds every frame of every video once, resized but neither flipped nor
+ * cropped; frame_row (nclips*T) int64 names the stored frame of each output frame, flip (nclips) uint8 mirrors a clip,
+ * crop_yx (nclips*T*2) int32 = the (row, column) crop origin per frame in the stored frame, or NULL for none (then out == src);
+ *   dst[b][t][c][y][x] = (frames[row][i + y][sx][c] / 255 - mean[c]) / std[c],  sx = flip[b] ? src_w - 1 - (j + x) : j + x,
+ * the arithmetic of vd_frames_normalize (bit-equal to it and to the host transform).  All three tables are DEVICE arrays, clips
+ * may share frames; mean3 / std3 are HOST pointers to 3 floats.  The caller validates the tables (rows inside the store, crops
+ * inside the frame); as a second guard a frame whose row or crop is out of range is skipped (its dst left untouched).
+ * -1 before any device call: a negative size, a NULL table / store / dst with non-zero work, a zero std, out > src, or
+ * out != src without crop_yx.  nclips == 0 returns 0.  HBM-bound: 15 bytes per pixel + one table row per frame; one launch. */
+int vd_clips_sample(const void* frames_u8, int64_t store_frames, int src_h, int src_w, const int64_t* frame_row,
+                    const int32_t* crop_yx, const uint8_t* flip, int64_t nclips, int T, int out_h, int out_w, float* dst,
+                    const float* mean3, const float* std3, void* stream);
+
 /* ---- Serialised tile programs: the torch-free, Python-free way to run a layer ------------------------------
  * A program blob is written offline by the planner (engine.export_program(plan) / tools/export_programs.py) for
  * one layer geometry; it replaces what nn.Conv3d/nn.ReLU/nn.MaxPool3d's constructors hold in the reference

@@ -8,7 +8,8 @@ epochs of the 8 parameter tensors, ``save_interval`` experts per file).  What di
 ``args.eval_mode`` undefined, so its first ``epoch()`` raises — it is 'SS' here; the real clips are decoded
 once and stay in HBM (``dataset.preload``; the reference's ``--preload`` keeps a host copy and its DataLoader re-uploads
 every batch), batches are device-side gathers in the DataLoader's shuffle order (``dataset.DeviceBatches``); there is no
-wandb.  Training itself is ``utils.epoch('train')`` = ``ConvNet3D.hip_train_step`` per batch
+wandb.  ``--train_videos resident`` keeps whole videos instead of one frozen draw per clip (``dataset.ResidentVideos``): the
+start frame stays cached and the flip is drawn on every read, which is the reference's loader without ``--preload``.  Training itself is ``utils.epoch('train')`` = ``ConvNet3D.hip_train_step`` per batch
 (``checkpoint.train_expert_trajectories``).
 """
 from __future__ import annotations
@@ -38,6 +39,9 @@ def build_parser():
     p.add_argument('--preload', action='store_true', help='accepted for compatibility: the clips are always HBM-resident')
     p.add_argument('--im_size', type=int, default=112)
     p.add_argument('--frames', type=int, default=16)
+    p.add_argument('--train_videos', type=str, default='preload', choices=['preload', 'resident'],
+                   help="preload: one draw per clip, frozen in HBM; resident: whole videos in HBM, the start cached and the flip "
+                        "drawn per read (the reference's loader without --preload)")
     return p
 
 
@@ -47,14 +51,20 @@ def run(args, train=None, num_classes=None, log=print):
     args.device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(args.device)
     args.eval_mode = 'SS'
+    loader = None
     if train is None:
         _, im_size, num_classes, _, _, _, dst_train, _, _ = D.get_dataset(args.dataset, args.data_path, img_size=(args.im_size, args.im_size))
-        clips, labels = D.preload(dst_train, args.device, workers=args.num_workers)
+        if getattr(args, 'train_videos', 'preload') == 'resident':
+            loader = D.resident_loader(dst_train, args.device, batch_size=args.batch_train, shuffle=True, workers=args.num_workers)
+            frames = D.NUM_FRAMES
+        else:
+            clips, labels = D.preload(dst_train, args.device, workers=args.num_workers)
     else:
         clips, labels = train
         im_size = tuple(clips.shape[-2:])
-    frames = int(clips.shape[1])
-    loader = D.DeviceBatches(clips, labels, args.batch_train, shuffle=True)
+    if loader is None:
+        frames = int(clips.shape[1])
+        loader = D.DeviceBatches(clips, labels, args.batch_train, shuffle=True)
     files, pending = [], []
     for it in range(args.num_experts):
         traj = checkpoint.train_expert_trajectories(

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "../../include/vd_hip.h"
+#include "frame_norm.h"
 
 typedef __bf16 bf16_t;
 
@@ -2402,11 +2403,7 @@ extern "C" int vd_abi_version(void) { return VD_ABI_VERSION; }
 // read and 12 written per pixel.  Every operation is a correctly rounded fp32 one, so the result equals the host
 // transform's bit for bit.
 // ------------------------------------------------------------------------------------------------------------------------
-struct FrameNorm { float mean[3]; float std[3]; };
-
-__device__ __forceinline__ float frame_norm1(unsigned v, float mean, float sd) {
-    return __fdiv_rn(__fsub_rn(__fdiv_rn((float)v, 255.0f), mean), sd);
-}
+// (FrameNorm / frame_norm1: frame_norm.h, shared with vd_clips_sample)
 
 __global__ void frames_normalize_quad_kernel(const uint32_t* __restrict__ src, float* __restrict__ dst, int64_t nframes,
                                              int64_t quads_per_frame, FrameNorm nm) {

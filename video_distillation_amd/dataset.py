@@ -17,6 +17,12 @@ resident, and the per-step gather is an index_select on the device (``distill.Re
 ``staticUCF50`` :738-839, ``singleKinetics400`` :18-77, ``singleSSv2`` :897-947): one frame of a video, repeated into a
 "boring" clip or handed out as an image.  They feed the reference's static-memory learning stage, which is off the hot
 path, so they are host-side only (no preload kernel of their own: an item is a clip or an image like any other).
+
+``preload`` freezes one draw per item.  Where the reference draws per READ -- a test item's start frame on every one of
+``epoch('test')``'s three passes, the flip of every item -- ``ResidentVideos`` keeps whole videos in HBM instead (every frame
+decoded once, uint8) and ``ResidentClipLoader`` draws each batch's frames / flips / crops on the host, in the DataLoader's
+generator order, and lets ``vd_clips_sample`` gather, mirror, crop and normalise them: the host loader's clips, bit for bit,
+without a JPEG decode per read.
 """
 from __future__ import annotations
 
@@ -94,6 +100,16 @@ class FrameTransform:
             image = image.resize((self.resize[1], self.resize[0]), Image.BILINEAR)
             i, j = crop
             image = image.crop((j, i, j + self.im_size[1], i + self.im_size[0]))
+        return np.asarray(image, dtype=np.uint8)
+
+    def stored_pixels(self, image) -> np.ndarray:
+        """PIL image -> (Hs, Ws, 3) uint8 after the deterministic part only (RGB conversion, resize): what ``ResidentVideos``
+        keeps per frame.  The flip and the crop of a read are applied to it on the device."""
+        from PIL import Image
+        if image.mode != 'RGB':
+            image = image.convert('RGB')
+        if self.resize is not None:
+            image = image.resize((self.resize[1], self.resize[0]), Image.BILINEAR)
         return np.asarray(image, dtype=np.uint8)
 
     def normalise(self, u8: torch.Tensor) -> torch.Tensor:
@@ -535,3 +551,322 @@ class DeviceBatches:
             yield self.clips.index_select(0, idx), self.labels.index_select(0, idx)
         if self.shuffle and self.generator is not None:
             torch.randperm(n, generator=self.generator)      # RandomSampler ends an epoch with a second (unused) permutation
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# HBM-resident whole videos, clips drawn per read on the device
+# ------------------------------------------------------------------------------------------------------------------------
+def sample_clips(frames: torch.Tensor, frame_row, flip, crop_yx, frames_per_clip: int, out_hw: Tuple[int, int],
+                 mean: Sequence[float], std: Sequence[float]):
+    """``vd_clips_sample`` on the current stream: ``frames`` (F, Hs, Ws, 3) uint8 on the device, HOST tables ``frame_row``
+    (nclips * T) / ``flip`` (nclips) / ``crop_yx`` (nclips * T, 2) or None -> a fresh (nclips, T, 3, H, W) fp32 tensor.
+
+    The tables are validated here, on the host (a row outside the store or a crop past the edge raises ``ValueError``: it
+    never reaches the device), packed into ONE pinned buffer and uploaded with one asynchronous copy; nothing synchronises."""
+    out, _ = _sample_clips(frames, frame_row, flip, crop_yx, frames_per_clip, out_hw, mean, std, None)
+    return out
+
+
+def check_clip_tables(store_frames: int, src_hw, out_hw, frame_row, flip, crop_yx, frames_per_clip: int):
+    """Host-side bounds check of the tables of one ``vd_clips_sample`` call -> (rows int64, flips uint8, crops int32 or None)
+    as contiguous numpy arrays.  ``ValueError`` for anything the kernel must not be handed."""
+    rows = np.ascontiguousarray(np.asarray(frame_row, dtype=np.int64).reshape(-1))
+    flips = np.ascontiguousarray(np.asarray(flip).astype(np.uint8).reshape(-1))
+    t = int(frames_per_clip)
+    (hs, ws), (oh, ow) = (int(v) for v in src_hw), (int(v) for v in out_hw)
+    if t <= 0 or rows.size != flips.size * t:
+        raise ValueError("clip tables: %d rows for %d clips of %d frames" % (rows.size, flips.size, t))
+    if oh > hs or ow > ws or oh < 0 or ow < 0:
+        raise ValueError("clip tables: output %s is larger than the stored frame %s" % ((oh, ow), (hs, ws)))
+    if rows.size and (rows.min() < 0 or rows.max() >= store_frames):
+        bad = int(rows[(rows < 0) | (rows >= store_frames)][0])
+        raise ValueError("clip tables: frame row %d is outside the store (%d frames)" % (bad, store_frames))
+    if crop_yx is None:
+        if (oh, ow) != (hs, ws):
+            raise ValueError("clip tables: output %s differs from the stored frame %s and there is no crop" % ((oh, ow), (hs, ws)))
+        return rows, flips, None
+    crops = np.ascontiguousarray(np.asarray(crop_yx, dtype=np.int64).reshape(-1, 2))
+    if crops.shape[0] != rows.size:
+        raise ValueError("clip tables: %d crop origins for %d frames" % (crops.shape[0], rows.size))
+    if crops.size and (crops.min() < 0 or crops[:, 0].max() > hs - oh or crops[:, 1].max() > ws - ow):
+        k = int(np.nonzero((crops[:, 0] < 0) | (crops[:, 1] < 0) | (crops[:, 0] > hs - oh) | (crops[:, 1] > ws - ow))[0][0])
+        raise ValueError("clip tables: crop origin %s + %s runs past the edge of the stored frame %s"
+                         % (tuple(int(v) for v in crops[k]), (oh, ow), (hs, ws)))
+    return rows, flips, crops.astype(np.int32)
+
+
+def _sample_clips(frames, frame_row, flip, crop_yx, frames_per_clip, out_hw, mean, std, extra):
+    """``sample_clips`` + ``extra``: an optional int64 host array that rides in the same upload (the batch's labels);
+    -> (clips, its device copy or None)."""
+    import ctypes
+    from . import hip
+    assert frames.dim() == 4 and frames.shape[3] == 3 and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.is_cuda
+    store_frames, hs, ws = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    t = int(frames_per_clip)
+    rows, flips, crops = check_clip_tables(store_frames, (hs, ws), (oh, ow), frame_row, flip, crop_yx, t)
+    b, nf = flips.size, rows.size
+    out = torch.empty((b, t, 3, oh, ow), dtype=torch.float32, device=frames.device)
+    ne = 0 if extra is None else int(np.asarray(extra).size)
+    if b == 0:
+        return out, (None if extra is None else torch.empty((0,), dtype=torch.int64, device=frames.device))
+    # one pinned buffer, 8-byte aligned sections: rows (int64) | crops (int32 pairs) | extra (int64) | flips (uint8).  A fresh
+    # pinned block per call: the caching host allocator hands it out again only after the copy below has finished.
+    o_crop = 8 * nf
+    o_extra = o_crop + (8 * nf if crops is not None else 0)
+    o_flip = o_extra + 8 * ne
+    host = torch.empty((o_flip + b,), dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    hv[:o_crop].view(np.int64)[:] = rows
+    if crops is not None:
+        hv[o_crop:o_extra].view(np.int32)[:] = crops.reshape(-1)
+    if ne:
+        hv[o_extra:o_flip].view(np.int64)[:] = np.asarray(extra, dtype=np.int64).reshape(-1)
+    hv[o_flip:] = flips
+    dev = host.to(frames.device, non_blocking=True)
+    base = dev.data_ptr()
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    with torch.cuda.device(frames.device):
+        hip.check(hip.lib().vd_clips_sample(hip.ptr(frames), ctypes.c_int64(store_frames), hs, ws, ctypes.c_void_p(base),
+                                            ctypes.c_void_p(base + o_crop if crops is not None else 0), ctypes.c_void_p(base + o_flip),
+                                            ctypes.c_int64(b), t, oh, ow, hip.ptr(out), m, s, hip.stream_ptr(frames.device)),
+                  "vd_clips_sample")
+    return out, (dev[o_extra:o_flip].view(torch.int64) if extra is not None else None)
+
+
+@dataclass
+class ResidentDraw:
+    """Everything random about one read of a resident video: frame NUMBERS (1-based, as in the file names), flip, crops."""
+    index: int
+    numbers: List[int]
+    flip: bool
+    crops: List[Optional[Tuple[int, int]]]
+
+
+class ResidentVideos:
+    """Every frame of every video of a 'window' dataset (UCF101, HMDB51, miniUCF101 -- 'split-random' included --, miniHMDB51),
+    decoded ONCE and kept in HBM as ``frames (F, Hs, Ws, 3) uint8``: RGB, resized when the transform resizes, neither flipped
+    nor cropped (PIL's flip and its bilinear resize commute byte for byte, so the flip of a read is a mirrored read of the
+    stored frame).  ``frame_offset (N+1)``, ``length (N)`` and ``labels`` stay on the host.  What a read draws -- start frame
+    per visit of a test item, segment picks, flip, crop origins -- is drawn per read by ``draw``, in the generator order of
+    ``FrameFolderVideos.draw``, and turned into a normalised batch by ``vd_clips_sample`` (``batch``): the clips the
+    reference's datasets produce, without a JPEG decode per read.
+
+    The constructor only lists directories (lengths, offsets, ``nbytes``); ``load`` decodes and uploads;
+    ``from_dataset`` does both."""
+
+    def __init__(self, dataset: FrameFolderVideos, indices: Optional[Sequence[int]] = None):
+        if isinstance(dataset, StillFrameVideos) or not isinstance(dataset, FrameFolderVideos):
+            raise ValueError("ResidentVideos: a still-frame dataset picks one frame per item and has no clip to draw per read; "
+                             "use dataset.preload")
+        if dataset.spec.pick != 'window':
+            raise ValueError("ResidentVideos: the %s family reads every listed frame of a video (no per-read frame choice); "
+                             "use dataset.preload" % dataset.family)
+        self.dataset = dataset
+        self.indices = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
+        self.slot = {i: k for k, i in enumerate(self.indices)}
+        self.length = [len(os.listdir(dataset.video_dirs[i])) for i in self.indices]
+        self.frame_offset = np.concatenate([[0], np.cumsum(self.length, dtype=np.int64)]).astype(np.int64)
+        self.labels = torch.tensor([dataset.labels[i] for i in self.indices], dtype=torch.int64)
+        tf = dataset.transform
+        self.out_hw = tuple(tf.im_size) if tf.resize is not None else None      # (None: the stored size, known below)
+        self._frame_hw = tuple(tf.resize) if tf.resize is not None else None
+        self.frames: Optional[torch.Tensor] = None
+        self.build_seconds = None
+
+    # -- sizes, from the listing alone ---------------------------------------------------------------------------------------
+    @property
+    def num_frames(self) -> int:
+        return int(self.frame_offset[-1])
+
+    @property
+    def frame_hw(self) -> Tuple[int, int]:
+        """Stored frame size: the transform's resize target, or the size in the header of the first frame file (no decode)."""
+        if self._frame_hw is None:
+            if not self.indices:
+                raise ValueError("ResidentVideos: an empty store has no frame size")
+            from PIL import Image
+            with Image.open(self._file(0, 1)) as im:
+                self._frame_hw = (im.height, im.width)
+        return self._frame_hw
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of ``frames``: F x Hs x Ws x 3."""
+        if not self.num_frames:
+            return 0
+        h, w = self.frame_hw
+        return self.num_frames * h * w * 3
+
+    def _file(self, slot: int, number: int) -> str:
+        return osp.join(self.dataset.video_dirs[self.indices[slot]], "frame{:06d}.jpg".format(number))
+
+    # -- build ---------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_dataset(cls, dataset: FrameFolderVideos, device, indices: Optional[Sequence[int]] = None, workers: int = 8,
+                     max_bytes: Optional[int] = None) -> "ResidentVideos":
+        return cls(dataset, indices).load(device, workers=workers, max_bytes=max_bytes)
+
+    def load(self, device, workers: int = 8, max_bytes: Optional[int] = None, chunk: int = 2048) -> "ResidentVideos":
+        """Decode every frame on ``workers`` host threads (16 at most) and copy it into HBM through a pinned double buffer on
+        a copy stream.  Refuses (``ValueError``, before anything is decoded) a store larger than ``max_bytes`` -- by default
+        half of the device's free memory."""
+        import time
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ResidentVideos: the store lives in HBM; use dataset[i] for host tensors")
+        need = self.nbytes
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(device)[0] // 2
+        if need > int(max_bytes):
+            raise ValueError("ResidentVideos: %d videos / %d frames need %d bytes of HBM, more than max_bytes = %d; build the store "
+                             "over fewer videos (indices=) or raise max_bytes" % (len(self.indices), self.num_frames, need, int(max_bytes)))
+        t0 = time.time()
+        nf = self.num_frames
+        if nf == 0:
+            self.frames = torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device)
+            self.build_seconds = 0.0
+            return self
+        h, w = self.frame_hw
+        if self.out_hw is None:
+            self.out_hw = (h, w)
+        tf = self.dataset.transform
+        frames = torch.empty((nf, h, w, 3), dtype=torch.uint8, device=device)
+        where = [(k, n) for k in range(len(self.indices)) for n in range(1, self.length[k] + 1)]      # store row -> (slot, number)
+        chunk = max(1, min(int(chunk), nf))
+        stage = [torch.empty((chunk, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        landed = [torch.cuda.Event() for _ in range(2)]
+        used = [False, False]
+        copy_stream = torch.cuda.Stream(device=device)
+        from PIL import Image
+
+        def decode_into(buf, k, row):
+            slot, number = where[row]
+            with Image.open(self._file(slot, number)) as im:
+                got = tf.stored_pixels(im)
+            if got.shape != (h, w, 3):
+                raise ValueError("ResidentVideos: %s is %s, the first frame %s (videos of mixed frame sizes cannot share a store)"
+                                 % (self._file(slot, number), got.shape[:2], (h, w)))
+            buf[k] = got
+
+        views = [s.numpy() for s in stage]                     # (numpy views of the pinned buffers: PIL's arrays are read-only)
+        with ThreadPoolExecutor(max_workers=max(1, min(int(workers), 16))) as pool:
+            for ci, lo in enumerate(range(0, nf, chunk)):
+                b = ci & 1
+                n = min(chunk, nf - lo)
+                if used[b]:
+                    landed[b].synchronize()                    # the pinned buffer may be overwritten
+                list(pool.map(lambda k: decode_into(views[b], k, lo + k), range(n)))
+                with torch.cuda.stream(copy_stream):
+                    frames[lo:lo + n].copy_(stage[b][:n], non_blocking=True)
+                    landed[b].record(copy_stream)
+                used[b] = True
+        copy_stream.synchronize()
+        self.frames = frames
+        self.build_seconds = time.time() - t0
+        return self
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+    # -- one read: the draws, then the tables --------------------------------------------------------------------------------
+    def draw(self, index: int) -> ResidentDraw:
+        """The draws of ``dataset[index]``, consumed from the global generators exactly as ``FrameFolderVideos.draw`` consumes
+        them (``np.random.randint`` for the start -- every visit of a test item, the first visit of any other --, the segment
+        picks of 'split-random', ``random.random()`` for the flip, ``torch.randint`` per frame when the transform crops), from
+        the cached lengths (no ``listdir``).  The start is the dataset's own ``start[index]``: host reads and resident reads of
+        one dataset see the same cached start."""
+        ds = self.dataset
+        index = int(index)
+        if index not in self.slot:
+            raise ValueError("ResidentVideos: item %d is not in the store" % index)
+        length = self.length[self.slot[index]]
+        skip = length // NUM_FRAMES if length < NUM_FRAMES * FRAME_GAP else FRAME_GAP
+        if ds.start[index] == -1 or ds.split == "test":
+            ds.start[index] = int(np.random.randint(1, length - (NUM_FRAMES - 1) * skip))
+        first = ds.start[index]
+        numbers = list(range(first, first + NUM_FRAMES * skip, skip))
+        if ds.family == 'miniUCF101' and ds.sample == 'split-random':
+            seg = length // 16
+            bounds = [(k * seg, (k + 1) * seg if k < 15 else length) for k in range(16)]
+            numbers = [int(np.random.randint(lo, hi)) + 1 for lo, hi in bounds]
+        flip = random.random() > 0.5
+        crops = [ds.transform.draw(0, 0) for _ in numbers]
+        return ResidentDraw(index, numbers, flip, crops)
+
+    def tables(self, draws: Sequence[ResidentDraw]):
+        """Host tables of a batch of draws -> ``(frame_row (b*T) int64, flip (b) uint8, crop_yx (b*T, 2) int32 or None)``,
+        validated against ``frame_offset`` / ``length`` and the crop bounds (``ValueError`` otherwise).  Needs no device."""
+        t = NUM_FRAMES
+        rows = np.empty((len(draws), t), dtype=np.int64)
+        flips = np.empty((len(draws),), dtype=np.uint8)
+        cropped = self.dataset.transform.resize is not None
+        crops = np.empty((len(draws), t, 2), dtype=np.int32) if cropped else None
+        for b, d in enumerate(draws):
+            if d.index not in self.slot:
+                raise ValueError("ResidentVideos: item %d is not in the store" % d.index)
+            slot = self.slot[d.index]
+            if len(d.numbers) != t:
+                raise ValueError("ResidentVideos: a draw of %d frames, clips have %d" % (len(d.numbers), t))
+            for n in d.numbers:
+                if not 1 <= int(n) <= self.length[slot]:
+                    raise ValueError("ResidentVideos: frame %d of %s is out of range (the video has %d frames)"
+                                     % (int(n), self.dataset.video_dirs[d.index], self.length[slot]))
+            rows[b] = self.frame_offset[slot] + np.asarray(d.numbers, dtype=np.int64) - 1
+            flips[b] = 1 if d.flip else 0
+            if cropped:
+                if len(d.crops) != t or any(c is None for c in d.crops):
+                    raise ValueError("ResidentVideos: the transform crops, a draw without %d crop origins" % t)
+                crops[b] = np.asarray(d.crops, dtype=np.int32)
+        out_hw = self.out_hw if self.out_hw is not None else self.frame_hw
+        return check_clip_tables(self.num_frames, self.frame_hw if self.num_frames else (0, 0), out_hw, rows.reshape(-1), flips,
+                                 None if crops is None else crops.reshape(-1, 2), t)
+
+    def batch(self, draws: Sequence[ResidentDraw]):
+        """-> ``(clips (b, T, 3, H, W) fp32, labels (b,) int64)`` on the store's device, fresh tensors; one table upload and
+        one ``vd_clips_sample`` launch on the current stream, no synchronisation."""
+        if self.frames is None:
+            raise RuntimeError("ResidentVideos: the store has not been loaded (from_dataset / load)")
+        rows, flips, crops = self.tables(draws)
+        tf = self.dataset.transform
+        labels = np.asarray([self.dataset.labels[d.index] for d in draws], dtype=np.int64)
+        return _sample_clips(self.frames, rows, flips, crops, NUM_FRAMES, self.out_hw, tf.mean.tolist(), tf.std.tolist(), labels)
+
+
+class ResidentClipLoader:
+    """Drop-in for ``DataLoader(dataset, batch_size, shuffle, num_workers=0)`` over a ``ResidentVideos`` store: iterating yields
+    ``(clips (b, T, 3, H, W) fp32, labels (b,) int64)`` on the store's device, the last batch short.  The global generators are
+    consumed exactly as the DataLoader iterating ``dataset[i]`` consumes them -- the iterator's base seed, the sampler's seed and
+    ``randperm`` (as ``DeviceBatches``), then the draws of every item in batch order -- so a seeded run sees the same clips either
+    way and leaves the generators in the same state."""
+
+    def __init__(self, store: ResidentVideos, batch_size: int = 64, shuffle: bool = False, generator=None):
+        self.store, self.dataset = store, store.dataset
+        self.batch_size, self.shuffle, self.generator = int(batch_size), bool(shuffle), generator
+
+    def __len__(self) -> int:
+        return (len(self.store) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        n = len(self.store)
+        torch.empty((), dtype=torch.int64).random_(generator=self.generator)          # the iterator's base seed
+        if self.shuffle:
+            if self.generator is None:
+                gen = torch.Generator()
+                gen.manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+            else:
+                gen = self.generator
+            order = torch.randperm(n, generator=gen).tolist()
+        else:
+            order = list(range(n))
+        for lo in range(0, n, self.batch_size):
+            yield self.store.batch([self.store.draw(self.store.indices[k]) for k in order[lo:lo + self.batch_size]])
+        if self.shuffle and self.generator is not None:
+            torch.randperm(n, generator=self.generator)      # RandomSampler ends an epoch with a second (unused) permutation
+
+
+def resident_loader(dataset: FrameFolderVideos, device, batch_size: int = 64, shuffle: bool = False, workers: int = 8,
+                    max_bytes: Optional[int] = None) -> ResidentClipLoader:
+    """``ResidentVideos.from_dataset`` + ``ResidentClipLoader`` in one call."""
+    return ResidentClipLoader(ResidentVideos.from_dataset(dataset, device, workers=workers, max_bytes=max_bytes), batch_size, shuffle)

@@ -16,7 +16,8 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvd_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernels.hip", "program.hip", "planner.cpp", "comm.cpp",
-                                                         "coreset.hip")]
+                                                         "coreset.hip", "clips_sample.hip")]
+CSRC_HEADERS = [os.path.join(_HERE, "csrc", "frame_norm.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
 HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
 
@@ -32,7 +33,8 @@ EXPORTS = ("vd_abi_version", "vd_conv_mfma", "vd_conv_mfma_multi", "vd_conv0_bre
            "vd_comm_free",
            "vd_bias_grad_pooled_scratch_floats", "vd_bias_grad_pooled_ordered", "vd_standardize_ordered", "vd_head_train_bwd_ordered",
            "vd_set_deterministic", "vd_get_deterministic", "vd_pack_weights_c8", "vd_pack_weights_multi",
-           "vd_split_scaled", "vd_scale_combine", "vd_sources_hash", "vd_coreset_workspace_bytes", "vd_coreset_select")
+           "vd_split_scaled", "vd_scale_combine", "vd_sources_hash", "vd_coreset_workspace_bytes", "vd_coreset_select",
+           "vd_clips_sample")
 F16X3_WSHIFT = 8          # include/vd_hip.h VD_F16X3_WSHIFT: packed fp16 hi+lo weights are W x 2^8, undone in the programs' epilogues
 
 
@@ -124,7 +126,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER)
+        key = _file_hash(src, HEADER, *CSRC_HEADERS)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -174,7 +176,7 @@ def sources_hash() -> str:
     measured on other kernels is refused instead of quoted."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER]:
+    for path in sorted(SOURCES) + [HEADER] + CSRC_HEADERS:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

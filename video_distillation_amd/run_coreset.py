@@ -47,6 +47,8 @@ def build_parser():
     p.add_argument('--im_size', type=int, default=112)
     p.add_argument('--num_classes', type=int, default=50, help='synthetic data only')
     p.add_argument('--pool_per_class', type=int, default=93, help='synthetic data only')
+    p.add_argument('--test_videos', type=str, default='host', choices=['host', 'resident'],
+                   help='resident: whole test videos in HBM, clips drawn per read on the device (run_dm.load_data)')
     # this driver's own
     p.add_argument('--kcenter', type=str, default='greedy', choices=['greedy', 'reference'])
     p.add_argument('--log_file', type=str, default=None)

@@ -6,7 +6,8 @@ distill_baseline.py:292-361, with its flag names for everything that branch read
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m video_distillation_amd.run_dm ...
 
 Data: ``--dataset synthetic`` (randn clips); ``--dataset miniUCF101|UCF101|HMDB51|Kinetics400 --data_path D``
-(the reference's frame folders, decoded once and kept in HBM: dataset.py); or ``--data_file f.pt`` holding
+(the reference's frame folders, decoded once and kept in HBM: dataset.py; ``--test_videos resident`` keeps the test split's
+whole videos there too, so that evaluation draws its clips per read without decoding JPEGs); or ``--data_file f.pt`` holding
 {"clips": (N,T,3,H,W), "labels": (N,), "test_clips", "test_labels"}.  Logging: JSON lines with the reference's wandb keys
 (``Loss``, ``Accuracy/<model>``, ``Max_Accuracy/<model>``, ``Std/<model>``, ``Max_Std/<model>``).
 """
@@ -50,6 +51,9 @@ def build_parser():
     p.add_argument('--prec_syn', type=str, default='f16x3')
     p.add_argument('--log_file', type=str, default=None)
     p.add_argument('--no_eval', action='store_true')
+    p.add_argument('--test_videos', type=str, default='host', choices=['host', 'resident'],
+                   help="host: the test loader decodes JPEGs per read; resident: whole test videos in HBM, clips drawn per read "
+                        "on the device (dataset.ResidentVideos; 'window' datasets only)")
     return p
 
 
@@ -58,8 +62,10 @@ def load_data(args, rank, world, geo, device):
     from . import distill
     if args.data_file is None and args.dataset != 'synthetic':
         from . import dataset as D
-        _, im_size, num_classes, _, _, _, dst_train, _, testloader = D.get_dataset(args.dataset, args.data_path,
-                                                                                   img_size=(args.im_size, args.im_size))
+        _, im_size, num_classes, _, _, _, dst_train, dst_test, testloader = D.get_dataset(args.dataset, args.data_path,
+                                                                                          img_size=(args.im_size, args.im_size))
+        if getattr(args, 'test_videos', 'host') == 'resident' and rank == 0:      # (rank 0 evaluates)
+            testloader = D.resident_loader(dst_test, device, batch_size=testloader.batch_size, workers=args.num_workers)
         c_lo, c_hi = distill.class_range(num_classes, rank, world)
         pool = distill.RealPool.from_dataset(dst_train, num_classes, list(range(c_lo, c_hi)), device, workers=args.num_workers)
         return pool, num_classes, (c_lo, c_hi), testloader
