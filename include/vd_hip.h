@@ -201,8 +201,11 @@ int vd_unpool_relu_bwd(const float* g, const uint8_t* argmax, int64_t nclips, in
                        int pool_t, int T, int OH, int OW, int g_layout, void* out_hi, void* out_lo,
                        int prec, const float* scale, void* stream);
 
-/* out[0] = 2^k with max|g| * 2^k in [target/2, target), out[1] = 2^-k (out[2] is scratch; out has
- * 4 floats).  Used to keep single-pass fp16 gradient operands inside fp16's exponent range. */
+/* out[0] = 2^k with max|g| * 2^k in [target/2, target), out[1] = 2^-k, out[2] = the float bits of max|g| (out has
+ * 4 floats).  Used to keep single-pass fp16 gradient operands inside fp16's exponent range.  k comes from the exponent and
+ * significand bits of max|g| and target (integer arithmetic): the half-open interval holds exactly, also where target / max|g| is
+ * a power of two and for a subnormal max|g|, as long as k lies in [-126, 126] -- k is clamped to that range so that 2^k and
+ * 2^-k are both normal floats.  All-zero input, a non-finite maximum or a target that is not positive and finite: scale 1. */
 int vd_absmax_scale(const float* g, int64_t n, float target, float* out, void* stream);
 
 /* DM class term, forward and gradient (distill_baseline.py:351):
@@ -216,7 +219,9 @@ int vd_dm_loss(const float* feat_real, const float* feat_syn, int nclass, int nr
 int vd_group_sum(const float* x, int groups, int per, int dim, float scale, float* out, void* stream);
 
 /* torch.optim.SGD(momentum, dampening 0) step on the synthetic pixels
- * (distill_baseline.py:107, 355): buf = first ? g : mu*buf + g ; x -= lr*buf. */
+ * (distill_baseline.py:107, 355): buf = first ? g : mu*buf + g ; x -= lr*buf.  Every multiplication and addition is rounded
+ * on its own (no fused multiply-add), here and in vd_sgd_momentum_wd (g' = g + wd*x first): the fp32 evaluation of the formula
+ * as written, bit for bit. */
 int vd_sgd_momentum(float* x, float* buf, const float* g, int64_t n, float lr, float momentum, int first,
                     void* stream);
 
@@ -234,7 +239,8 @@ int vd_hallucinator_bwd(const float* g_out, const float* stat, const float* dyn,
 
 /* match_loss / distance_wb row reductions (utils.py:634-687).  For one gradient tensor viewed
  * as [rows][len]: acc[0] += sum_rows (1 - <r,s>/(|r||s|+1e-6)), acc[1] += sum (s-r)^2,
- * acc[2] += <r,s>, acc[3] += |r|^2, acc[4] += |s|^2.  acc is 5 fp32 (fp32 atomics). */
+ * acc[2] += <r,s>, acc[3] += |r|^2, acc[4] += |s|^2.  acc is 5 fp32 (fp32 atomics).  [rows][len] is a ROW view for every len,
+ * len == 1 included (each element its own cosine row, as in the _multi form below); forward and backward agree on that. */
 int vd_match_rows_fwd(const float* gr, const float* gs, int64_t rows, int len, float* acc, void* stream);
 /* d/d gs of the three metrics; mode 0 'ours' (row cosine), 1 'mse', 2 'cos' (needs the global
  * sums in acc as produced by the forward).  gout = upstream scalar gradient. */

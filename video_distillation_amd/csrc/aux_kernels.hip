@@ -448,16 +448,40 @@ __global__ void absmax_kernel(const float* __restrict__ g, int64_t n, unsigned i
     }
 }
 
-__global__ void scale_from_absmax_kernel(const unsigned int* __restrict__ bits, float target, float* __restrict__ out) {
-    const float m = __uint_as_float(bits[0]);
-    float s = 1.f;
-    if (m > 0.f && m < 3.0e38f) {
-        int e = (int)floorf(log2f(target / m));
-        e = e < -100 ? -100 : (e > 100 ? 100 : e);
-        s = ldexpf(1.f, e);
+// value = mant * 2^(e - 23) with mant in [2^23, 2^24): exponent and significand of a positive finite float from its bits
+// (subnormals normalised), so that the scale's exponent is integer arithmetic -- no log2f rounding at powers of two, no overflow
+// of target / m for a subnormal maximum
+__device__ __forceinline__ void float_decompose(unsigned int bits, int& e, unsigned int& mant) {
+    e = (int)(bits >> 23);
+    mant = bits & 0x7fffffu;
+    if (e == 0) {
+        const int sh = __clz(mant) - 8;
+        mant <<= sh;
+        e = 1 - sh;
+    } else {
+        mant |= 0x800000u;
     }
-    out[0] = s;
-    out[1] = 1.f / s;
+    e -= 127;
+}
+
+__global__ void scale_from_absmax_kernel(const unsigned int* __restrict__ bits, float target, float* __restrict__ out) {
+    const unsigned int mb = bits[0], tb = __float_as_uint(target);
+    int k = 0;       // scale 1: all-zero input, non-finite maximum, target not positive and finite
+    if (mb != 0u && mb < 0x7f800000u && tb != 0u && tb < 0x7f800000u) {
+        int em, et;
+        unsigned int mm, mt;
+        float_decompose(mb, em, mm);
+        float_decompose(tb, et, mt);
+        // the largest k with m * 2^k < target: significand of target above m's -> the exponent difference, else one less
+        // (equal significands: m * 2^(et - em) == target, outside the half-open interval)
+        k = et - em - (mt > mm ? 0 : 1);
+        // the widest clamp under which 2^k and 2^-k are both normal floats.  (+-100, the clamp of the log2f version, would
+        // break the interval for a maximum near FLT_MAX: 3e38 against a target of 1024 needs k = -118.)  A scale that far out
+        // has no headroom left for a product with another scale (vd_scale_combine mode 0); the interval is what is promised.
+        k = k < -126 ? -126 : (k > 126 ? 126 : k);
+    }
+    out[0] = __uint_as_float((unsigned int)(127 + k) << 23);
+    out[1] = __uint_as_float((unsigned int)(127 - k) << 23);
 }
 
 extern "C" int vd_absmax_scale(const float* g, int64_t n, float target, float* out, void* stream) {
@@ -550,10 +574,14 @@ __global__ void sgd_momentum_kernel(float* __restrict__ x, float* __restrict__ b
                                     int64_t n, float lr, float mu, int first) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        // every operation rounded on its own (no fused multiply-add): the fp32 evaluation of the header's formula as written
+#pragma clang fp contract(off)
         const float gv = g[i];
-        const float b = first ? gv : buf[i] * mu + gv;
+        const float prev = buf[i] * mu;
+        const float b = first ? gv : prev + gv;
         buf[i] = b;
-        x[i] -= lr * b;
+        const float step = lr * b;
+        x[i] = x[i] - step;
     }
 }
 
@@ -1282,7 +1310,7 @@ __device__ __forceinline__ void match_rows_fwd_body(const float* __restrict__ gr
 
 __global__ __launch_bounds__(VD_MATCH_FWD_THREADS) void match_rows_fwd_kernel(const float* __restrict__ gr, const float* __restrict__ gs,
                                                               int64_t rows, int len, float* __restrict__ acc) {
-    match_rows_fwd_body(gr, gs, rows, len, acc, gridDim.x, len == 1);
+    match_rows_fwd_body(gr, gs, rows, len, acc, gridDim.x, false);      // [rows][len] is a ROW view for every len (vd_hip.h)
 }
 
 // all tensors of a gradient list in ONE launch: blockIdx.y = segment (a match_loss call used to be 8 launches of
@@ -1310,7 +1338,7 @@ extern "C" int vd_match_rows_fwd_multi(const VdMatchBatch* b, float* acc, void* 
 
 extern "C" int vd_match_rows_fwd(const float* gr, const float* gs, int64_t rows, int len, float* acc, void* stream) {
     if (rows <= 0 || len <= 0) return 0;
-    const int64_t blocks = vd_match_blocks(rows, len);
+    const int64_t blocks = vd_match_blocks(rows, len == 1 ? 2 : len);      // len == 1: one-element cosine rows, not a flat sum
     hipLaunchKernelGGL(match_rows_fwd_kernel, dim3((unsigned)blocks), dim3(VD_MATCH_FWD_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                        gr, gs, rows, len, acc);
     return (int)hipGetLastError();
@@ -2242,11 +2270,16 @@ __global__ void sgd_wd_kernel(float* __restrict__ x, float* __restrict__ buf, co
                               float mu, float wd, int first) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        // every operation rounded on its own (no fused multiply-add), as in sgd_momentum_kernel
+#pragma clang fp contract(off)
         const float p = x[i];
-        const float gv = g[i] + wd * p;
-        const float bnew = first ? gv : buf[i] * mu + gv;
+        const float decay = wd * p;
+        const float gv = g[i] + decay;
+        const float prev = buf[i] * mu;
+        const float bnew = first ? gv : prev + gv;
         buf[i] = bnew;
-        x[i] = p - lr * bnew;
+        const float step = lr * bnew;
+        x[i] = p - step;
     }
 }
 
@@ -2261,38 +2294,63 @@ extern "C" int vd_sgd_momentum_wd(float* x, float* buf, const float* g, int64_t 
 }
 
 // Batch-global standardisation of epoch() (utils.py:770): out = (x - mean(x)) / std(x), unbiased std.
-__global__ void sum_sumsq_kernel(const float* __restrict__ x, int64_t n, double* __restrict__ acc) {
-    __shared__ float red[16];
-    float s = 0.f, q = 0.f;
+// Sum and sum of squares are accumulated in fp64 from the first add on (a float's square is exact in fp64), so that the
+// one-pass variance (sum x^2 - n mean^2) / (n - 1) keeps ~1e-10 even at |mean| / std = 1000, where fp32 partial sums lost
+// 2.5e-2 of the output to the cancellation.  Per element that is two conversions and two fp64 adds in the first kernel and two
+// conversions, an fp64 subtract and multiply in the second, against 4 + 8 bytes of HBM traffic.
+__device__ __forceinline__ double block_sum_d(double v, double* red) {      // result valid in thread 0; fixed association
+    v = wave_sum_d(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0) {
+        const int nw = (blockDim.x + 63) >> 6;
+        for (int i = 0; i < nw; ++i) t += red[i];
+    }
+    return t;
+}
+
+__device__ __forceinline__ void sum_sumsq_thread(const float* __restrict__ x, int64_t n, double& s, double& q) {
+    s = 0.0; q = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v = x[i];
+        const double v = (double)x[i];
         s += v; q += v * v;
     }
-    const float ts = block_sum(s, red);
-    const float tq = block_sum(q, red);
-    if (threadIdx.x == 0) { atomicAdd(&acc[0], (double)ts); atomicAdd(&acc[1], (double)tq); }
+}
+
+// out = (x - mean) / std with the subtraction in fp64 and ONE rounding to fp32 (a float mean of 1000 is itself off by up to 3e-5)
+__device__ __forceinline__ void standardize_apply(const float* __restrict__ x, int64_t n, double sum, double sumsq, float* __restrict__ out) {
+    const double mean = sum / (double)n;
+    const double var = (sumsq - (double)n * mean * mean) / (double)(n - 1);
+    const double inv = 1.0 / sqrt(var);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = (float)(((double)x[i] - mean) * inv);
+}
+
+__global__ void sum_sumsq_kernel(const float* __restrict__ x, int64_t n, double* __restrict__ acc) {
+    __shared__ double red[16];
+    double s, q;
+    sum_sumsq_thread(x, n, s, q);
+    const double ts = block_sum_d(s, red);
+    const double tq = block_sum_d(q, red);
+    if (threadIdx.x == 0) { atomicAdd(&acc[0], ts); atomicAdd(&acc[1], tq); }
 }
 
 __global__ void standardize_kernel(const float* __restrict__ x, int64_t n, const double* __restrict__ acc, float* __restrict__ out) {
-    const double mean = acc[0] / (double)n;
-    const double var = (acc[1] - (double)n * mean * mean) / (double)(n - 1);
-    const float m = (float)mean, inv = (float)(1.0 / sqrt(var));
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = (x[i] - m) * inv;
+    standardize_apply(x, n, acc[0], acc[1], out);
 }
 
 // Ordered mode: every block writes its two partial sums to its own slot; every block of the second kernel folds the slots in
 // the same fixed order (lane-strided, then a fixed shuffle tree), so mean and std do not depend on the order blocks retire in.
 __global__ void sum_sumsq_partial_kernel(const float* __restrict__ x, int64_t n, double* __restrict__ part) {
-    __shared__ float red[16];
-    float s = 0.f, q = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v = x[i];
-        s += v; q += v * v;
-    }
-    const float ts = block_sum(s, red);
-    const float tq = block_sum(q, red);
-    if (threadIdx.x == 0) { part[2 * blockIdx.x] = (double)ts; part[2 * blockIdx.x + 1] = (double)tq; }
+    __shared__ double red[16];
+    double s, q;
+    sum_sumsq_thread(x, n, s, q);
+    const double ts = block_sum_d(s, red);
+    const double tq = block_sum_d(q, red);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = ts; part[2 * blockIdx.x + 1] = tq; }
 }
 
 __global__ void standardize_ordered_kernel(const float* __restrict__ x, int64_t n, const double* __restrict__ part, int nparts,
@@ -2305,11 +2363,7 @@ __global__ void standardize_ordered_kernel(const float* __restrict__ x, int64_t 
         if (threadIdx.x == 0) { tot[0] = s; tot[1] = q; }
     }
     __syncthreads();
-    const double mean = tot[0] / (double)n;
-    const double var = (tot[1] - (double)n * mean * mean) / (double)(n - 1);
-    const float m = (float)mean, inv = (float)(1.0 / sqrt(var));
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = (x[i] - m) * inv;
+    standardize_apply(x, n, tot[0], tot[1], out);
 }
 
 // vd_standardize with a fixed summation order; `scratch` holds VD_STANDARDIZE_ORDERED_SCRATCH (4096) doubles, caller-owned.
