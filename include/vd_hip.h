@@ -332,6 +332,16 @@ int vd_standardize_ordered(const float* x, int64_t n, double* scratch, float* ou
 int vd_head_train_bwd_ordered(const float* dlogits, const int32_t* amax_t, const float* dropped, const float* mask, const float* w,
                               int64_t nclips, int C, int To, int Ho, int Wo, int kt, int kh, int kw, int K, float* g_w, float* g_b,
                               float* g_feats, void* stream);
+/* The statistics epoch('test') keeps per batch (utils.py:793-824), one launch, ACCUMULATED (+=) into the fp64 record
+ * rec[8 + 2K] (csrc/eval_stats.hip):
+ *   [0] clips seen   [1] sum of per-clip cross-entropy (fp64 softmax of the fp32 logits, as vd_ce_loss)
+ *   [2] [3] [4] top-1 / top-3 / top-5 hits   [5] clips whose label is outside [0, K) (counted here and nowhere else)
+ *   [6] [7] zero   [8 .. 8+K) top-1 hits per class   [8+K .. 8+2K) clips per class
+ * rank of a clip = classes with a strictly greater logit than the label's + classes with an equal logit at a lower index;
+ * top-k hit <=> rank < k (top-1 == argmax with first-maximum semantics == label; K <= k: every valid clip hits).  The batch's
+ * cross-entropy sum is formed in a fixed order and added by one thread, the counts are integers: a record is bitwise
+ * reproducible.  B == 0: returns 0, nothing touched.  -1 (before any device call): B < 0, K < 1, or a NULL pointer with B > 0. */
+int vd_eval_stats(const float* logits, const int64_t* labels, int B, int K, double* rec, void* stream);
 /* Process-wide accumulation-order switch (initial value: environment VD_DETERMINISTIC=1, else 0).  While it is on,
  * weight-gradient programs PLANNED by the library (vd_program_build_wgrad, vd_train_create) give every box of positions its
  * own accumulation copy -- an fp32 atomic add onto a zeroed word with one contributor is exact, vd_replica_sum then folds the

@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvd_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernels.hip", "program.hip", "planner.cpp", "comm.cpp",
-                                                         "coreset.hip", "clips_sample.hip")]
+                                                         "coreset.hip", "clips_sample.hip", "eval_stats.hip")]
 CSRC_HEADERS = [os.path.join(_HERE, "csrc", "frame_norm.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
 HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
@@ -34,7 +34,7 @@ EXPORTS = ("vd_abi_version", "vd_conv_mfma", "vd_conv_mfma_multi", "vd_conv0_bre
            "vd_bias_grad_pooled_scratch_floats", "vd_bias_grad_pooled_ordered", "vd_standardize_ordered", "vd_head_train_bwd_ordered",
            "vd_set_deterministic", "vd_get_deterministic", "vd_pack_weights_c8", "vd_pack_weights_multi",
            "vd_split_scaled", "vd_scale_combine", "vd_sources_hash", "vd_coreset_workspace_bytes", "vd_coreset_select",
-           "vd_clips_sample")
+           "vd_clips_sample", "vd_eval_stats")
 F16X3_WSHIFT = 8          # include/vd_hip.h VD_F16X3_WSHIFT: packed fp16 hi+lo weights are W x 2^8, undone in the programs' epilogues
 
 
@@ -259,6 +259,53 @@ def ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
 
 def is_x3(prec: int) -> bool:
     return prec >= 2
+
+
+EVAL_STATS_HEAD = 8          # include/vd_hip.h vd_eval_stats: scalar slots in front of the two per-class blocks
+
+
+def eval_stats_record(num_classes: int, device=None) -> torch.Tensor:
+    """A zeroed record for ``eval_stats``: 8 + 2K doubles (layout: include/vd_hip.h)."""
+    return torch.zeros(EVAL_STATS_HEAD + 2 * int(num_classes), dtype=torch.float64, device=device)
+
+
+def eval_stats(logits: torch.Tensor, labels: torch.Tensor, rec: torch.Tensor) -> torch.Tensor:
+    """Accumulate the test statistics of one batch -- clips, cross-entropy sum, top-1/3/5 hits, labels out of range, hits and
+    clips per class -- into ``rec`` (vd_eval_stats, one launch on the current stream).  Device tensors always go to the kernel;
+    CPU tensors take the same definitions in torch fp64 (as utils._standardize does for CPU tensors: the host logic of
+    evalpool.py then runs under gloo without a GPU)."""
+    if logits.dim() != 2:
+        raise ValueError("eval_stats: logits (B, K)")
+    B, K = int(logits.shape[0]), int(logits.shape[1])
+    if K < 1 or tuple(labels.shape) != (B,) or rec.dtype != torch.float64 or rec.numel() != EVAL_STATS_HEAD + 2 * K \
+            or not rec.is_contiguous():
+        raise ValueError("eval_stats: logits (B, K), labels (B,), rec %d contiguous doubles" % (EVAL_STATS_HEAD + 2 * K))
+    if logits.device != labels.device or logits.device != rec.device:
+        raise ValueError("eval_stats: logits, labels and rec live on one device")
+    z = logits.detach().to(torch.float32).contiguous()
+    y = labels.detach().to(torch.int64).contiguous()
+    if z.is_cuda:
+        check(lib().vd_eval_stats(ptr(z), ptr(y), B, K, ptr(rec), stream_ptr(z.device)), "vd_eval_stats")
+        return rec
+    if B == 0:
+        return rec
+    valid = (y >= 0) & (y < K)
+    rec[5] += float((~valid).sum())
+    z, y = z[valid].double(), y[valid]
+    if y.numel() == 0:
+        return rec
+    zy = z.gather(1, y[:, None])
+    index = torch.arange(K)[None, :]
+    rank = ((z > zy) | ((z == zy) & (index < y[:, None]))).sum(1)
+    m = z.max(dim=1, keepdim=True).values
+    ce = (m + torch.log(torch.exp(z - m).sum(1, keepdim=True)) - zy)[:, 0]
+    rec[0] += float(y.numel())
+    rec[1] += ce.sum()
+    for slot, k in ((2, 1), (3, 3), (4, 5)):
+        rec[slot] += float((rank < k).sum())
+    rec[EVAL_STATS_HEAD:EVAL_STATS_HEAD + K] += torch.bincount(y[rank < 1], minlength=K).double()
+    rec[EVAL_STATS_HEAD + K:] += torch.bincount(y, minlength=K).double()
+    return rec
 
 
 class Comm:

@@ -54,6 +54,12 @@ def build_parser():
     p.add_argument('--test_videos', type=str, default='host', choices=['host', 'resident'],
                    help="host: the test loader decodes JPEGs per read; resident: whole test videos in HBM, clips drawn per read "
                         "on the device (dataset.ResidentVideos; 'window' datasets only)")
+    p.add_argument('--eval_ranks', type=str, default='rank0', choices=['rank0', 'all'],
+                   help="rank0: rank 0 trains and tests the num_eval networks one after the other; all: the networks and their "
+                        "three test passes are dealt over all ranks (evalpool.evaluate_pool)")
+    p.add_argument('--eval_seed', type=int, default=None,
+                   help="--eval_ranks all: seed of the evaluation networks (default: a clock value drawn on rank 0); the "
+                        "evaluation at iteration `it` uses eval_seed + it")
     return p
 
 
@@ -64,7 +70,8 @@ def load_data(args, rank, world, geo, device):
         from . import dataset as D
         _, im_size, num_classes, _, _, _, dst_train, dst_test, testloader = D.get_dataset(args.dataset, args.data_path,
                                                                                           img_size=(args.im_size, args.im_size))
-        if getattr(args, 'test_videos', 'host') == 'resident' and rank == 0:      # (rank 0 evaluates)
+        # (rank 0 evaluates; with --eval_ranks all every rank does)
+        if getattr(args, 'test_videos', 'host') == 'resident' and (rank == 0 or getattr(args, 'eval_ranks', 'rank0') == 'all'):
             testloader = D.resident_loader(dst_test, device, batch_size=testloader.batch_size, workers=args.num_workers)
         c_lo, c_hi = distill.class_range(num_classes, rank, world)
         pool = distill.RealPool.from_dataset(dst_train, num_classes, list(range(c_lo, c_hi)), device, workers=args.num_workers)
@@ -126,6 +133,17 @@ def run(args, backend=None, log=None):
             if out:
                 out.write(line + "\n"); out.flush()
 
+    eval_all = getattr(args, 'eval_ranks', 'rank0') == 'all' and not args.no_eval
+    eval_seed = None
+    if eval_all:
+        eval_seed = getattr(args, 'eval_seed', None)
+        if eval_seed is None:
+            box = [int(time.time() * 1000) % 100000 if rank == 0 else None]
+            if world > 1:
+                import torch.distributed as dist
+                dist.broadcast_object_list(box, src=0)
+            eval_seed = box[0]
+        emit({"eval_ranks": "all", "eval_seed": int(eval_seed), "world": world})
     eval_its = set(np.arange(0, args.Iteration + 1, args.eval_it).tolist())
     t0 = time.time()
     for it in range(args.Iteration + 1):
@@ -133,7 +151,25 @@ def run(args, backend=None, log=None):
             syn_all = trainer.gather_syn()
             trainer.sync()
             save_best = False
-            if rank == 0 and testloader is not None:
+            if eval_all and testloader is not None:
+                from . import evalpool
+                label_syn = torch.arange(num_classes).repeat_interleave(args.ipc)
+                eargs = argparse.Namespace(device=str(device), lr_net=args.lr_net, epoch_eval_train=args.epoch_eval_train,
+                                           batch_train=args.batch_train, model=args.model, eval_mode=args.eval_mode)
+                for model_eval in eval_pool:
+                    if model_eval != 'ConvNet3D':
+                        raise NotImplementedError("--eval_ranks all evaluates ConvNet3D (the hot path's network), not %s" % model_eval)
+                    make_net = evalpool.convnet3d_factory(num_classes, (args.im_size, args.im_size), args.frames)
+                    got = evalpool.evaluate_pool(make_net, syn_all.detach().clone(), label_syn, testloader, eargs, num_eval=args.num_eval,
+                                                 seed=int(eval_seed) + it, mode='none', rank=rank, world=world, num_classes=num_classes)
+                    mean, std = got["mean"], got["std"]           # (the same numbers on every rank: best_* stay in step)
+                    if mean > best_acc[model_eval]:
+                        best_acc[model_eval], best_std[model_eval], save_best = mean, std, True
+                    emit({"step": it, "Accuracy/%s" % model_eval: mean, "Max_Accuracy/%s" % model_eval: best_acc[model_eval],
+                          "Std/%s" % model_eval: std, "Max_Std/%s" % model_eval: best_std[model_eval]})
+                    emit({"step": it, "eval_pool": {"train_s": got["times"]["train_s"], "test_pass_s": got["times"]["test_pass_s"],
+                                                    "assignment": got["assignment"]}})
+            elif rank == 0 and testloader is not None:
                 label_syn = torch.arange(num_classes).repeat_interleave(args.ipc)
                 for model_eval in eval_pool:
                     accs = []
