@@ -231,6 +231,16 @@ int vd_sgd_momentum(float* x, float* buf, const float* g, int64_t n, float lr, f
 int vd_hallucinator_fwd(const float* stat, const float* dyn, const int64_t* sidx, const int64_t* didx,
                         const float* w, const float* b, int n, int T, int H, int W, float* out, void* stream);
 
+/* The same with one hallucinator per output clip (MultiStaticSharedDataset, utils.py:462-496):
+ * out[i] = conv3d(cat(static[sidx[i]] repeated over T, dynamic[didx[i]]), w[hidx[i]], b[hidx[i]]), bit for bit what
+ * vd_hallucinator_fwd gives for item i alone with set hidx[i].  w [nh][3][4][27], b [nh][3]; hidx NULL = set 0 for every
+ * clip, sidx / didx NULL = identity.  One launch on a 2-D grid (clip, pixel columns): the set is uniform per workgroup.
+ * -1: a NULL stat / dyn / w / b / out or nh <= 0; -2: n > 65535 (both before any device call).  Indices are NOT checked on
+ * the device: the caller validates 0 <= hidx[i] < nh and the gather rows (hip.hallucinate_multi does). */
+int vd_hallucinator_fwd_multi(const float* stat, const float* dyn, const int64_t* sidx, const int64_t* didx,
+                              const int32_t* hidx, const float* w, const float* b, int nh, int n, int T, int H, int W,
+                              float* out, void* stream);
+
 /* Its backward: g_dyn (scatter-added into [nd][T][1][H][W], pre-zeroed by the caller),
  * g_stat (optional, [ns][3][H][W], pre-zeroed), g_w [3*4*27], g_b [3] (pre-zeroed). */
 int vd_hallucinator_bwd(const float* g_out, const float* stat, const float* dyn, const int64_t* sidx,

@@ -609,19 +609,13 @@ extern "C" int vd_sgd_momentum(float* x, float* buf, const float* g, int64_t n, 
 // (3 + T + 3 T) * H * W * 4.
 #define HAL_W(co, ci, kt, kh, kw) w[(((co) * 4 + (ci)) * 3 + (kt)) * 9 + (kh) * 3 + (kw)]
 
-__global__ __launch_bounds__(256) void hal_fwd_kernel(const float* __restrict__ stat, const float* __restrict__ dyn,
-                                                       const int64_t* __restrict__ sidx, const int64_t* __restrict__ didx,
-                                                       const float* __restrict__ w, const float* __restrict__ b,
-                                                       int n, int T, int H, int W, float* __restrict__ out) {
-    const int64_t total = (int64_t)n * H * W;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int x = (int)(i % W);
-    const int y = (int)((i / W) % H);
-    const int64_t clip = i / ((int64_t)W * H);
-    const int64_t si = sidx ? sidx[clip] : clip, di = didx ? didx[clip] : clip;
-    const float* sp = stat + si * 3 * H * W;
-    const float* dp = dyn + di * (int64_t)T * H * W;
+// The column walk of both forward kernels: output clip `clip`, pixel column `pix` = y * W + x of it, `sp` / `dp` the static
+// image and the dynamic memory the clip is composed from, `w` / `b` its hallucinator (wave-uniform in both callers).
+__device__ __forceinline__ void hal_fwd_column(int64_t clip, int pix, const float* __restrict__ sp, const float* __restrict__ dp,
+                                               const float* __restrict__ w, const float* __restrict__ b, int T, int H, int W,
+                                               float* __restrict__ out) {
+    const int x = pix % W;
+    const int y = pix / W;
     bool ok[9];
     int off[9];
 #pragma unroll
@@ -676,6 +670,48 @@ __global__ __launch_bounds__(256) void hal_fwd_kernel(const float* __restrict__ 
 #pragma unroll
         for (int k = 0; k < 9; ++k) { d[0][k] = d[1][k]; d[1][k] = d[2][k]; }
     }
+}
+
+__global__ __launch_bounds__(256) void hal_fwd_kernel(const float* __restrict__ stat, const float* __restrict__ dyn,
+                                                       const int64_t* __restrict__ sidx, const int64_t* __restrict__ didx,
+                                                       const float* __restrict__ w, const float* __restrict__ b,
+                                                       int n, int T, int H, int W, float* __restrict__ out) {
+    const int64_t total = (int64_t)n * H * W;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int64_t clip = i / ((int64_t)W * H);
+    const int64_t si = sidx ? sidx[clip] : clip, di = didx ? didx[clip] : clip;
+    hal_fwd_column(clip, (int)(i % ((int64_t)W * H)), stat + si * 3 * H * W, dyn + di * (int64_t)T * H * W, w, b, T, H, W, out);
+}
+
+// One hallucinator per clip (MultiStaticSharedDataset, utils.py:462-496): blockIdx.y = clip, blockIdx.x over its H*W pixel
+// columns, so the set index hidx[blockIdx.y] -- and with it every one of the 324 weight addresses -- is block-uniform and the
+// weights stay on the scalar path.  (Under the 1-D grid above a wave may span two clips: a per-thread set would turn the 81
+// scalar operands per frame into vector loads.)
+__global__ __launch_bounds__(256) void hal_fwd_multi_kernel(const float* __restrict__ stat, const float* __restrict__ dyn,
+                                                             const int64_t* __restrict__ sidx, const int64_t* __restrict__ didx,
+                                                             const int32_t* __restrict__ hidx, const float* __restrict__ w,
+                                                             const float* __restrict__ b, int T, int H, int W,
+                                                             float* __restrict__ out) {
+    const int pix = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (pix >= H * W) return;
+    const int64_t clip = blockIdx.y;
+    const int64_t si = sidx ? sidx[clip] : clip, di = didx ? didx[clip] : clip;
+    const int set = hidx ? hidx[clip] : 0;
+    hal_fwd_column(clip, pix, stat + si * 3 * H * W, dyn + di * (int64_t)T * H * W, w + (int64_t)set * 324, b + (int64_t)set * 3,
+                   T, H, W, out);
+}
+
+extern "C" int vd_hallucinator_fwd_multi(const float* stat, const float* dyn, const int64_t* sidx, const int64_t* didx,
+                                         const int32_t* hidx, const float* w, const float* b, int nh, int n, int T, int H, int W,
+                                         float* out, void* stream) {
+    if (!stat || !dyn || !w || !b || !out || nh <= 0) return -1;
+    if (n > 65535) return -2;          // gridDim.y
+    if (n <= 0 || T <= 0 || H <= 0 || W <= 0) return 0;
+    const int64_t hw = (int64_t)H * W;
+    hipLaunchKernelGGL(hal_fwd_multi_kernel, dim3((unsigned)((hw + 255) / 256), (unsigned)n), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), stat, dyn, sidx, didx, hidx, w, b, T, H, W, out);
+    return (int)hipGetLastError();
 }
 
 extern "C" int vd_hallucinator_fwd(const float* stat, const float* dyn, const int64_t* sidx, const int64_t* didx,

@@ -977,6 +977,24 @@ class S2DTrainer:
 
     global_loss = DMTrainer.global_loss
 
+    def gather_memories(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Every class's static rows (C*spc,3,H,W) and dynamic memories (C,dpc,T,1,H,W) in class order on every rank
+        (evaluation / ``dynamic_*.pt``); the hallucinator is identical on all ranks already.  Waits for the steps still in
+        flight first, as ``DMTrainer.gather_syn`` does; one rank gets views of its shards."""
+        self.sync()
+        shape_d = (-1, self.dpc) + tuple(self.dynamic.shape[1:])
+        if not collectives_on(self.world):
+            return self.static, self.dynamic.view(shape_d)
+        counts = [b - a for a, b in (class_range(self.num_classes, r, self.world) for r in range(self.world))]
+        out = []
+        for shard, per in ((self.static, self.spc), (self.dynamic, self.dpc)):
+            pad = torch.zeros((max(counts) * per,) + tuple(shard.shape[1:]), dtype=shard.dtype, device=shard.device)
+            pad[:shard.shape[0]] = shard
+            parts = [torch.empty_like(pad) for _ in range(self.world)]
+            _all_gather(parts, pad)
+            out.append(torch.cat([p[:c * per] for p, c in zip(parts, counts)], dim=0))      # class blocks are contiguous per rank
+        return out[0], out[1].view(shape_d)
+
     def mark(self):
         ev = torch.cuda.Event(enable_timing=True)
         ev.record(self.be.s_syn if getattr(self.be, "two_streams", False) else torch.cuda.current_stream(self.dynamic.device))

@@ -98,12 +98,12 @@ def train_network(net: nn.Module, images_train, labels_train, args, mode: str = 
     optimizer = torch.optim.SGD(net.parameters(), lr=lr, momentum=0.9, weight_decay=0.0005)
     criterion = nn.CrossEntropyLoss().to(args.device)
     if mode == 'none':
-        dst_train = utils.TensorDataset(images_train, labels_train)
+        trainloader = torch.utils.data.DataLoader(utils.TensorDataset(images_train, labels_train), batch_size=args.batch_train,
+                                                  shuffle=True, num_workers=0)
     elif mode == 'multi-static':
-        dst_train = utils.MultiStaticSharedDataset(images_train[0], images_train[1], images_train[2])
+        trainloader = utils.multi_static_loader(images_train[0], images_train[1], images_train[2], args.batch_train)
     else:
         raise NotImplementedError
-    trainloader = torch.utils.data.DataLoader(dst_train, batch_size=args.batch_train, shuffle=True, num_workers=0)
     loss_train, acc_train = 0.0, 0.0
     for ep in range(Epoch + 1):
         loss_train, acc_train, _ = utils.epoch('train', trainloader, net, optimizer, criterion, args)

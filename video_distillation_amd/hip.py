@@ -34,7 +34,7 @@ EXPORTS = ("vd_abi_version", "vd_conv_mfma", "vd_conv_mfma_multi", "vd_conv0_bre
            "vd_bias_grad_pooled_scratch_floats", "vd_bias_grad_pooled_ordered", "vd_standardize_ordered", "vd_head_train_bwd_ordered",
            "vd_set_deterministic", "vd_get_deterministic", "vd_pack_weights_c8", "vd_pack_weights_multi",
            "vd_split_scaled", "vd_scale_combine", "vd_sources_hash", "vd_coreset_workspace_bytes", "vd_coreset_select",
-           "vd_clips_sample", "vd_eval_stats")
+           "vd_clips_sample", "vd_eval_stats", "vd_hallucinator_fwd_multi")
 F16X3_WSHIFT = 8          # include/vd_hip.h VD_F16X3_WSHIFT: packed fp16 hi+lo weights are W x 2^8, undone in the programs' epilogues
 
 
@@ -306,6 +306,73 @@ def eval_stats(logits: torch.Tensor, labels: torch.Tensor, rec: torch.Tensor) ->
     rec[EVAL_STATS_HEAD:EVAL_STATS_HEAD + K] += torch.bincount(y[rank < 1], minlength=K).double()
     rec[EVAL_STATS_HEAD + K:] += torch.bincount(y, minlength=K).double()
     return rec
+
+
+def check_hallucinator_tables(ns: int, nd: int, nh: int, sidx, didx, hidx):
+    """Host-side bounds check of the index tables of one ``vd_hallucinator_fwd_multi`` call -> (sidx int64, didx int64,
+    hidx int32) as contiguous numpy arrays of one length.  ``ValueError`` for anything the kernel must not be handed (it does
+    not check its indices)."""
+    import numpy as np
+    s = np.ascontiguousarray(np.asarray(sidx, dtype=np.int64).reshape(-1))
+    d = np.ascontiguousarray(np.asarray(didx, dtype=np.int64).reshape(-1))
+    h = np.ascontiguousarray(np.asarray(hidx, dtype=np.int64).reshape(-1))
+    if not s.size == d.size == h.size:
+        raise ValueError("hallucinator tables: %d static, %d dynamic and %d hallucinator indices" % (s.size, d.size, h.size))
+    for name, t, hi in (("sidx", s, ns), ("didx", d, nd), ("hidx", h, nh)):
+        if t.size and (t.min() < 0 or t.max() >= hi):
+            raise ValueError("hallucinator tables: %s %d is outside [0, %d)" % (name, int(t[(t < 0) | (t >= hi)][0]), hi))
+    return s, d, h.astype(np.int32)
+
+
+def hallucinate_multi(static: torch.Tensor, dynamic: torch.Tensor, sidx, didx, hidx, weights: torch.Tensor, biases: torch.Tensor,
+                      extra=None):
+    """``vd_hallucinator_fwd_multi`` on the current stream: out[i] = hallucinator ``hidx[i]`` over (static[sidx[i]],
+    dynamic[didx[i]]).  ``static`` (ns, 3, H, W), ``dynamic`` (nd, T, 1, H, W), ``weights`` (nh, 3, 4, 3, 3, 3) and ``biases``
+    (nh, 3) are contiguous fp32 tensors on one device; ``sidx`` / ``didx`` / ``hidx`` are HOST tables of one length n.
+    -> a fresh (n, T, 3, H, W) fp32 tensor, or (that, the device copy of ``extra``) when ``extra`` -- an int64 host array of
+    n entries that rides in the same upload, e.g. the batch's labels -- is given.
+
+    The tables are validated here, on the host (``ValueError``: an index out of range never reaches the device), packed into
+    ONE pinned buffer and uploaded with one asynchronous copy; nothing synchronises."""
+    import numpy as np
+    if static.dim() != 4 or dynamic.dim() != 5 or static.shape[1] != 3 or dynamic.shape[2] != 1 \
+            or tuple(static.shape[2:]) != tuple(dynamic.shape[3:]):
+        raise ValueError("hallucinate_multi: static (ns, 3, H, W) and dynamic (nd, T, 1, H, W)")
+    nh = int(weights.shape[0]) if weights.dim() == 6 else 0
+    if nh < 1 or tuple(weights.shape[1:]) != (3, 4, 3, 3, 3) or tuple(biases.shape) != (nh, 3):
+        raise ValueError("hallucinate_multi: weights (nh, 3, 4, 3, 3, 3) and biases (nh, 3)")
+    s, d, h = check_hallucinator_tables(int(static.shape[0]), int(dynamic.shape[0]), nh, sidx, didx, hidx)
+    n, (T, H, W) = s.size, (int(dynamic.shape[1]), int(dynamic.shape[3]), int(dynamic.shape[4]))
+    if n > 65535:
+        raise ValueError("hallucinate_multi: %d clips in one launch (at most 65535)" % n)
+    e = None if extra is None else np.asarray(extra, dtype=np.int64).reshape(-1)
+    if e is not None and e.size != n:
+        raise ValueError("hallucinate_multi: extra holds %d entries for %d clips" % (e.size, n))
+    for t in (static, dynamic, weights, biases):
+        if not (t.is_cuda and t.device == dynamic.device and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("hallucinate_multi has no CPU path: contiguous fp32 tensors on one HIP device")
+    dev = dynamic.device
+    out = torch.empty((n, T, 3, H, W), dtype=torch.float32, device=dev)
+    ne = 0 if e is None else n
+    if n == 0:
+        return out if e is None else (out, torch.as_tensor(e).to(dev))
+    # one pinned buffer: sidx (int64) | didx (int64) | extra (int64) | hidx (int32).  A fresh pinned block per call: the
+    # caching host allocator hands it out again only after the copy below has finished.
+    o_d, o_e, o_h = 8 * n, 16 * n, 16 * n + 8 * ne
+    host = torch.empty((o_h + 4 * n,), dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    hv[:o_d].view(np.int64)[:] = s
+    hv[o_d:o_e].view(np.int64)[:] = d
+    if ne:
+        hv[o_e:o_h].view(np.int64)[:] = e
+    hv[o_h:].view(np.int32)[:] = h
+    tab = host.to(dev, non_blocking=True)
+    base = tab.data_ptr()
+    with torch.cuda.device(dev):
+        check(lib().vd_hallucinator_fwd_multi(ptr(static), ptr(dynamic), ctypes.c_void_p(base), ctypes.c_void_p(base + o_d),
+                                              ctypes.c_void_p(base + o_h), ptr(weights), ptr(biases), nh, n, T, H, W, ptr(out),
+                                              stream_ptr(dev)), "vd_hallucinator_fwd_multi")
+    return out if e is None else (out, tab[o_e:o_h].view(torch.int64))
 
 
 class Comm:

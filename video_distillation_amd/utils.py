@@ -107,7 +107,10 @@ class MultiStaticSharedDataset(Dataset):
         self.n_s = static.shape[0]
         self.n_c, self.dpc = dynamic.shape[0], dynamic.shape[1]
 
-    def __getitem__(self, index):
+    def draw(self, index):
+        """Everything random about item ``index`` -> (label, static_idx, dynamic_idx, hal_idx): row of the static memory, row
+        of the class's dynamic memories, position in the hallucinator list.  Three ``random.randint`` calls, in
+        ``__getitem__``'s order (static, dynamic, hallucinator)."""
         per_s = self.n_s // self.n_c
         if per_s == 10:
             label, idx = index // 5, index % 5
@@ -120,7 +123,11 @@ class MultiStaticSharedDataset(Dataset):
         else:
             print("error for multi-static-shared-dataset")
             exit()
-        hal = self.hallucinator[random.randint(0, len(self.hallucinator) - 1)]
+        return label, static_idx, dynamic_idx, random.randint(0, len(self.hallucinator) - 1)
+
+    def __getitem__(self, index):
+        label, static_idx, dynamic_idx, hal_idx = self.draw(index)
+        hal = self.hallucinator[hal_idx]
         video = hal(self.static[static_idx].unsqueeze(0), self.dynamic[label, dynamic_idx].unsqueeze(0))
         return video[0], label
 
@@ -197,6 +204,95 @@ class Conv3DNet(nn.Module):
         elif tuple(weight.shape) != (3, 4, 3, 3, 3):
             raise NotImplementedError("HIP hallucinator is built for Conv3d(4->3, k=3)")
         return _HallucinatorFunction.apply(static, dynamic, weight, self.encoder.bias)
+
+
+def hallucinator_operand(hal):
+    """(weight (3,4,3,3,3), bias (3,)) of a ``Conv3DNet`` as its ``forward`` hands them to the kernel -- the same expressions, so
+    the same bits -- or None for anything else (another module or callable, a ``mode`` or Conv3d shape the kernel is not built
+    for)."""
+    if not isinstance(hal, Conv3DNet) or not isinstance(getattr(hal, "encoder", None), nn.Conv3d) or hal.encoder.bias is None:
+        return None
+    weight = hal.encoder.weight
+    if hal.mode == 'add':
+        if tuple(weight.shape) != (3, 3, 3, 3, 3):
+            return None
+        weight = torch.cat([weight, weight.sum(1, keepdim=True)], 1)
+    elif hal.mode != 'concat' or tuple(weight.shape) != (3, 4, 3, 3, 3):
+        return None
+    return weight.detach().float().contiguous(), hal.encoder.bias.detach().float().contiguous()
+
+
+class MultiStaticBatches:
+    """What ``DataLoader(MultiStaticSharedDataset(static, dynamic, hallucinators), batch_size, shuffle, num_workers=0)``
+    yields, composed on the device: the draws of a whole batch are made on the host (``MultiStaticSharedDataset.draw`` per
+    item in batch order, so Python's ``random`` is consumed as the dataset consumes it), uploaded in one copy, and the batch is
+    ONE ``vd_hallucinator_fwd_multi`` launch without gradient -- instead of one single-clip launch, one ``unsqueeze`` pair
+    and one ``torch.stack`` operand per item.  The shuffle consumes the global torch generator exactly as the DataLoader does
+    (``dataset.DeviceBatches``).  Yields (clips (b, T, 3, H, W) fp32, labels (b,) int64), both on the memories' device, bit
+    for bit the host loader's batches; the last batch is short.
+
+    The memories live on a HIP device and every hallucinator is a ``Conv3DNet`` the kernel is built for
+    (``device_composable``); the weight table is read from the modules at the start of every epoch."""
+
+    def __init__(self, static, dynamic, hallucinators, batch_size: int, shuffle: bool = True, generator=None):
+        if not self.device_composable(static, dynamic, hallucinators):
+            raise ValueError("MultiStaticBatches: memories on one HIP device and Conv3DNet hallucinators of a built shape "
+                             "('concat' 4->3 or 'add' 3->3, k = 3); anything else goes through the DataLoader")
+        self.dataset = MultiStaticSharedDataset(static, dynamic, hallucinators)
+        self.batch_size, self.shuffle, self.generator = int(batch_size), bool(shuffle), generator
+        self._static = self.dataset.static.contiguous()
+        self._dynamic = self.dataset.dynamic.contiguous().view((-1,) + tuple(dynamic.shape[2:]))      # row = label * dpc + dynamic_idx
+
+    @staticmethod
+    def device_composable(static, dynamic, hallucinators) -> bool:
+        if not (torch.is_tensor(static) and torch.is_tensor(dynamic) and static.is_cuda and dynamic.is_cuda
+                and static.device == dynamic.device and static.dim() == 4 and dynamic.dim() == 6):
+            return False
+        try:
+            hals = list(hallucinators)
+        except TypeError:
+            return False
+        return len(hals) > 0 and all(hallucinator_operand(h) is not None and h.encoder.weight.device == dynamic.device
+                                     for h in hals)
+
+    def __len__(self) -> int:
+        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        n = len(self.dataset)
+        torch.empty((), dtype=torch.int64).random_(generator=self.generator)          # the iterator's base seed
+        if self.shuffle:
+            if self.generator is None:
+                gen = torch.Generator()
+                gen.manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+            else:
+                gen = self.generator
+            order = torch.randperm(n, generator=gen).tolist()
+        else:
+            order = list(range(n))
+        with torch.no_grad():
+            operands = [hallucinator_operand(h) for h in self.dataset.hallucinator]
+            weights = torch.stack([w for w, _ in operands]).contiguous()
+            biases = torch.stack([b for _, b in operands]).contiguous()
+        dpc = self.dataset.dpc
+        for lo in range(0, n, self.batch_size):
+            draws = [self.dataset.draw(i) for i in order[lo:lo + self.batch_size]]
+            with torch.no_grad():
+                yield hip.hallucinate_multi(self._static, self._dynamic, [d[1] for d in draws], [d[0] * dpc + d[2] for d in draws],
+                                            [d[3] for d in draws], weights, biases, extra=[d[0] for d in draws])
+        if self.shuffle and self.generator is not None:
+            torch.randperm(n, generator=self.generator)      # RandomSampler ends an epoch with a second (unused) permutation
+
+
+def multi_static_loader(static, dynamic, hallucinators, batch_size: int):
+    """The training loader of ``evaluate_synset(mode='multi-static')``: batches composed on the device when the memories live
+    there and every hallucinator is one the kernel is built for, the ``DataLoader`` over ``MultiStaticSharedDataset`` for
+    anything else (CPU tensors, arbitrary callables).  Both yield the same batches and leave the generators in the same
+    state."""
+    if MultiStaticBatches.device_composable(static, dynamic, hallucinators):
+        return MultiStaticBatches(static, dynamic, hallucinators, batch_size, shuffle=True)
+    return torch.utils.data.DataLoader(MultiStaticSharedDataset(static, dynamic, hallucinators), batch_size=batch_size,
+                                       shuffle=True, num_workers=0)
 
 
 # ------------------------------------------------------------------------------------------
@@ -399,12 +495,12 @@ def evaluate_synset(it_eval, net, images_train, labels_train, testloader, args, 
     optimizer = torch.optim.SGD(net.parameters(), lr=lr, momentum=0.9, weight_decay=0.0005)
     criterion = nn.CrossEntropyLoss().to(args.device)
     if mode == 'none':
-        dst_train = TensorDataset(images_train, labels_train)
+        trainloader = torch.utils.data.DataLoader(TensorDataset(images_train, labels_train), batch_size=args.batch_train,
+                                                  shuffle=True, num_workers=0)
     elif mode == 'multi-static':
-        dst_train = MultiStaticSharedDataset(images_train[0], images_train[1], images_train[2])
+        trainloader = multi_static_loader(images_train[0], images_train[1], images_train[2], args.batch_train)
     else:
         raise NotImplementedError
-    trainloader = torch.utils.data.DataLoader(dst_train, batch_size=args.batch_train, shuffle=True, num_workers=0)
     start = time.time()
     acc_test, acc_per = None, None
     for ep in range(Epoch + 1):
