@@ -1,8 +1,11 @@
-"""The C-ABI shared library loads and exports every symbol include/vd_hip.h declares
+"""The C-ABI shared library loads and exports every symbol include/vd_hip.h declares, the binding takes every signature from
+that header, and the ctypes struct mirrors have the layout the compiler gives the header's structs
 (no compute calls: there is no GPU in the CPU test tier)."""
 import ctypes
+import glob
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -24,19 +27,16 @@ def test_library_exports_every_declared_symbol():
     from video_distillation_amd import hip
     if not os.path.exists(hip.LIB_PATH):
         hip.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
+    lib = hip.bind(hip.LIB_PATH)
     for name in declared_functions():
         assert hasattr(lib, name), name
-    lib.vd_abi_version.restype = ctypes.c_int
     assert lib.vd_abi_version() == 5
 
 
 def test_argument_errors_are_reported_before_any_device_call():
     """Entry points validate their arguments first (codes -1 / -2, include/vd_hip.h) -- callable without a GPU."""
     from video_distillation_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        hip.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
+    lib = hip.lib()
     assert lib.vd_conv_mfma(None, None) == -1
     assert lib.vd_conv_mfma_multi(None, 2, None) == -1
     a, b = hip.VdConvParams(), hip.VdConvParams()
@@ -59,7 +59,7 @@ def test_argument_errors_are_reported_before_any_device_call():
 
 def test_params_struct_layout_matches_header():
     """ctypes mirror of VdConvParams: same field order as the C struct (names must appear in the
-    header in the same sequence) and the size hipcc computes for it."""
+    header in the same sequence); offsets and sizes: test_struct_mirrors_have_the_compiler_s_layout."""
     from video_distillation_amd import hip
     text = open(os.path.join(ROOT, "include", "vd_hip.h")).read()
     body = text[text.index("typedef struct VdConvParams {") + len("typedef struct VdConvParams {"):text.index("} VdConvParams;")]
@@ -73,6 +73,113 @@ def test_params_struct_layout_matches_header():
         names += [re.sub(r"\[.*\]", "", n.strip().lstrip("*")) for n in decl.split(",")]
     assert names == [f[0] for f in hip.VdConvParams._fields_]
     assert ctypes.sizeof(hip.VdConvParams) % 8 == 0
+
+
+def _prototype_text():
+    """include/vd_hip.h without comments, struct bodies and #define lines."""
+    text = open(os.path.join(ROOT, "include", "vd_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"\{[^{}]*\}", "", text)
+    return re.sub(r"^\s*#\s*define.*$", "", text, flags=re.M)
+
+
+def test_every_prototype_of_the_header_is_parsed():
+    from video_distillation_amd import hip
+    assert len(hip.signatures()) == len(re.findall(r"vd_[a-z0-9_]+\(", _prototype_text())) == 86
+    assert hip.EXPORTS == tuple(hip.signatures())
+    defined = []
+    csrc = os.path.join(ROOT, "video_distillation_amd", "csrc")
+    for path in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")):
+        defined += re.findall(r'extern\s+"C"\s+(?:const\s+)?\w+\s*\*?\s*(vd_[a-z0-9_]+)\s*\(', open(path).read())
+    assert sorted(defined) == sorted(hip.signatures())
+
+
+def test_signatures_pinned_by_hand():
+    from video_distillation_amd import hip
+    i, q, f, p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+    pinned = {
+        "vd_unpool_relu_bwd": (i, [p, p, q, i, i, i, i, i, i, i, i, i, p, p, i, p, p]),
+        "vd_program_run": (i, [p, p, q, p, p, q, p, p, i, p]),
+        "vd_sgd_momentum": (i, [p, p, p, q, f, f, i, p]),
+        "vd_train_step": (i, [p, p, p, p, p, p, f, f, f, i, p, q, p, p, p]),
+        "vd_conv_mfma_multi": (i, [p, i, p]),
+        "vd_bias_grad_pooled_scratch_floats": (q, [q, i, q]),
+        "vd_sources_hash": (ctypes.c_char_p, []),
+        "vd_blob_free": (None, [p]),
+    }
+    assert len(pinned["vd_unpool_relu_bwd"][1]) == 17
+    for name, want in pinned.items():
+        assert hip.signatures()[name] == want, name
+    lib = hip.lib()
+    for name, (restype, argtypes) in hip.signatures().items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
+@pytest.mark.parametrize("text,quoted", [
+    ("int vd_a(int n);\nint vd_b(float* x, unsigned long n, void* stream);\n", "unsigned long n"),
+    ("int vd_a(int n);\nint vd_b(void (*done)(int), void* stream);\n", "void (*done)(int)"),
+    ("int vd_a(int n);\nint vd_b(const float* x, int64_t n,\n", "vd_b(const float* x, int64_t n,"),
+    ("int vd_a(uint8_t flag);\n", "uint8_t flag"),
+    ("float vd_a(int n);\n", "float vd_a(int n)"),
+    ("int vd_a(int n);\nint vd_a(int64_t n);\n", "int vd_a(int64_t n)"),
+])
+def test_the_parser_refuses_what_it_does_not_know(text, quoted):
+    from video_distillation_amd import hip
+    with pytest.raises(ValueError) as e:
+        hip.parse_header("/* a header */\n#include <stdint.h>\n" + text)
+    assert quoted in str(e.value)
+
+
+def test_plain_python_ints_travel_in_the_declared_width():
+    from video_distillation_amd import hip
+    assert hip.lib().vd_bias_grad_pooled_scratch_floats(2 ** 33, 8, 256) == 2 ** 36
+
+
+def test_wrong_arguments_are_exceptions_before_the_call():
+    from video_distillation_amd import hip
+    lib = hip.lib()
+    with pytest.raises(TypeError):
+        lib.vd_bias_grad_pooled_scratch_floats(2, 8)
+    with pytest.raises(TypeError):
+        lib.vd_bias_grad_pooled_scratch_floats(2, 8, 256, 0)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.vd_group_sum(None, 1, 1, 1, ctypes.c_double(1.0), None, None)           # a double into `float scale`
+    with pytest.raises(ctypes.ArgumentError):
+        lib.vd_bias_grad_pooled_scratch_floats(2, ctypes.c_int64(8), 256)           # 64 bits into `int C`
+    with pytest.raises(RuntimeError, match=r"^vd_conv_mfma\(level0\) failed with code -1$"):
+        hip.run("vd_conv_mfma", None, None, what="vd_conv_mfma(level0)")
+    with pytest.raises(RuntimeError, match=r"^vd_conv_mfma failed with code -1$"):
+        hip.run("vd_conv_mfma", None, None)
+
+
+def _mirror_fields(struct):
+    return [(name, getattr(struct, name).offset, getattr(struct, name).size) for name, *_ in struct._fields_]
+
+
+def test_struct_mirrors_have_the_compiler_s_layout(tmp_path):
+    """A host program compiled from the header prints sizeof of the five structs the binding mirrors and offsetof / size of
+    every field the mirrors name; the ctypes layout must be the same, and so must the two array bounds."""
+    from video_distillation_amd import hip
+    structs = [hip.VdConvParams, hip.VdMatchSeg, hip.VdMatchBatch, hip.VdPackSeg, hip.VdPackBatch]
+    lines = ['#include <cstddef>', '#include <cstdio>', '#include "vd_hip.h"', 'int main() {',
+             '    std::printf("VD_PACK_MAX %d\\nVD_MATCH_MAX_SEG %d\\n", VD_PACK_MAX, VD_MATCH_MAX_SEG);']
+    for s in structs:
+        n = s.__name__
+        lines.append('    std::printf("%s %%zu\\n", sizeof(%s));' % (n, n))
+        for f, _, _ in _mirror_fields(s):
+            lines.append('    std::printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (n, f, n, f, n, f))
+    lines += ['    return 0;', '}']
+    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    got = dict(line.split(None, 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    want = {"VD_PACK_MAX": "%d" % hip.VD_PACK_MAX, "VD_MATCH_MAX_SEG": "%d" % hip.VD_MATCH_MAX_SEG}
+    for s in structs:
+        want[s.__name__] = "%d" % ctypes.sizeof(s)
+        for f, offset, size in _mirror_fields(s):
+            want["%s.%s" % (s.__name__, f)] = "%d %d" % (offset, size)
+    assert got == want
 
 
 def test_product_has_no_cpu_fallback():
@@ -101,8 +208,7 @@ def test_library_carries_the_hash_of_its_sources_and_a_stale_one_is_refused(tmp_
     hip.build()
     want = hip.sources_hash()
     assert hip.library_stamp() == want and len(want) == 16
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    lib.vd_sources_hash.restype = ctypes.c_char_p
+    lib = hip.bind(hip.LIB_PATH)
     assert lib.vd_sources_hash().decode() == hip.STAMP_PREFIX + want
     # a copy of the library next to "touched" sources (one byte appended to a copy of a kernel file): the stamp no longer matches
     stale = tmp_path / "libvd_hip.so"

@@ -78,9 +78,7 @@ def test_greedy_kcenter_is_farthest_point():
 def _lib():
     from video_distillation_amd import hip
     hip.build()
-    L = ctypes.CDLL(hip.LIB_PATH)
-    L.vd_coreset_workspace_bytes.restype = ctypes.c_int64
-    return L
+    return hip.bind(hip.LIB_PATH)
 
 
 def test_coreset_entry_points_check_arguments_before_any_device_call():

@@ -26,8 +26,7 @@ def _cpp_blob(lib, layer, geo, prec, hint):
                                             ((8, 64, 64), "bf16x3", 8), ((8, 64, 64), "f16x3", 256), ((8, 80, 96), "f16", 4),
                                             ((4, 64, 64), "f16x3", None)])
 def test_cpp_planner_emits_the_python_planner_s_programs(dims, prec, hint):
-    lib = ctypes.CDLL(LIB)
-    lib.vd_blob_free.restype = None
+    lib = hip.bind(LIB)
     geo = plan.NetGeometry(*dims)
     x3 = prec.endswith("x3")
     net = plan.plan_network(geo, ntw=2, ntw0=1, balanced=not x3, batch_hint=hint)
@@ -40,7 +39,7 @@ def test_cpp_planner_emits_the_python_planner_s_programs(dims, prec, hint):
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libvd_hip.so not built")
 def test_cpp_planner_argument_errors():
-    lib = ctypes.CDLL(LIB)
+    lib = hip.bind(LIB)
     blob, n = ctypes.c_void_p(), ctypes.c_int64()
     assert lib.vd_program_build(3, 16, 112, 112, 1, 0, ctypes.byref(blob), ctypes.byref(n)) == -1
     assert lib.vd_program_build(0, 16, 112, 112, 7, 0, ctypes.byref(blob), ctypes.byref(n)) == -1
@@ -53,8 +52,7 @@ def test_cpp_planner_argument_errors():
 def test_cpp_planner_emits_the_python_planner_s_input_gradient_programs(dims, hint, monkeypatch):
     if hint == 50:       # one combination with the 2 x 2 pixel blocks of rounds 1-3 (both planners read the same switch)
         monkeypatch.setenv("VD_BWD0_WIDE", "0")
-    lib = ctypes.CDLL(LIB)
-    lib.vd_blob_free.restype = None
+    lib = hip.bind(LIB)
     geo = plan.NetGeometry(*dims)
     net = plan.plan_network(geo, ntw=2, ntw0=1, balanced=True, batch_hint=hint)
     assert net["bwd"][0][0].meta["block_w"] == (2 if hint == 50 else 4) and net["bwd"][0][0].n_out == (12 if hint == 50 else 24)
@@ -80,8 +78,7 @@ def test_cpp_planner_emits_the_python_planner_s_weight_gradient_programs(dims, n
     """vd_program_build_wgrad == plan.plan_wgrad: the same block of positions, the same accumulation copies, byte-identical
     serialised programs, for every layer of the benchmark geometries and an odd one, both operand-plane counts, batch sizes
     from a ragged handful to 256."""
-    lib = ctypes.CDLL(LIB)
-    lib.vd_blob_free.restype = None
+    lib = hip.bind(LIB)
     geo = plan.NetGeometry(*dims)
     for layer, (cin, cout, t, h, w) in enumerate([d[:5] for d in geo.layer_dims()]):
         pl = plan.plan_wgrad("wgrad%dx%d" % (cin, cout), cin, cout, t, h, w, nclips, planes=planes)

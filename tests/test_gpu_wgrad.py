@@ -106,7 +106,7 @@ def test_weight_gradient_through_the_c_abi_alone(layer, n, prec):
     blob, nb, block, reps = ctypes.c_void_p(), ctypes.c_int64(), (ctypes.c_int * 3)(), ctypes.c_int()
     hip.check(L.vd_program_build_wgrad(layer, 8, 64, 64, n, planes, ctypes.byref(blob), ctypes.byref(nb), block, ctypes.byref(reps)), "build")
     prog = ctypes.c_void_p()
-    hip.check(L.vd_program_load(blob, nb, hip.PREC[prec], ctypes.byref(prog)), "load")
+    hip.check(L.vd_program_load(blob, nb.value, hip.PREC[prec], ctypes.byref(prog)), "load")
     L.vd_blob_free(blob)
     try:
         T, OH, OW = y.shape[2:]

@@ -215,9 +215,7 @@ def test_clips_sample_argument_errors_come_before_any_device_call():
     from video_distillation_amd import hip
     if not os.path.exists(hip.LIB_PATH):
         hip.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    fn = lib.vd_clips_sample
-    fn.restype = ctypes.c_int
+    fn = hip.bind(hip.LIB_PATH).vd_clips_sample
     p = ctypes.c_void_p(4096)                            # never dereferenced: every call below returns before a launch
     null = ctypes.c_void_p(0)
     mean = (ctypes.c_float * 3)(0.485, 0.456, 0.406)

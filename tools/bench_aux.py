@@ -2,7 +2,7 @@
 """HBM-bound side kernels of the path: achieved GB/s of algorithmic bytes vs the
 8 TB/s HBM3E peak -- hallucinator fwd/bwd, match_loss fwd/bwd, DM loss, pixel SGD, pix2rows.
 Prints one JSON object."""
-import ctypes, json, os, sys, types
+import json, os, sys, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from video_distillation_amd import hip, utils, distill, plan
@@ -68,7 +68,7 @@ def main():
     xx = torch.randn(512, 16, 3, 112, 112, device=dev)
     rows = torch.empty(512 * 48 * 112 * 15, 8, dtype=torch.int16, device=dev)
     L = hip.lib()
-    t = timeit(lambda: L.vd_pix2rows(hip.ptr(xx), None, ctypes.c_int64(512), 16, 112, 112, hip.ptr(rows), None, 1, hip.stream_ptr(dev)))
+    t = timeit(lambda: L.vd_pix2rows(hip.ptr(xx), None, 512, 16, 112, 112, hip.ptr(rows), None, 1, hip.stream_ptr(dev)))
     byt = xx.numel() * 4 + rows.numel() * 2
     out["pix2rows_f16"] = {"ms": t * 1e3, "GBps": byt / t / 1e9, "frac_hbm": byt / t / 1e9 / PEAK}
     # decoded frames -> clips (dataset preload): 256 clips x 16 frames 112x112, 3 B read + 12 B written per pixel

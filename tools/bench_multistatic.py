@@ -113,15 +113,15 @@ def bench_kernels(hip, dev, n, n_hal, launches, reps):
     didx = torch.randint(0, nd, (n,), generator=g).to(dev)
     hidx = torch.randint(0, n_hal, (n,), generator=g).to(torch.int32).to(dev)
     out = torch.empty((n, T, 3, H, W), dtype=torch.float32, device=dev)
-    L, st = hip.lib(), hip.stream_ptr(dev)
+    st = hip.stream_ptr(dev)
 
     def multi():
-        hip.check(L.vd_hallucinator_fwd_multi(hip.ptr(static), hip.ptr(dynamic), hip.ptr(sidx), hip.ptr(didx), hip.ptr(hidx), hip.ptr(w),
-                                              hip.ptr(b), n_hal, n, T, H, W, hip.ptr(out), st), "vd_hallucinator_fwd_multi")
+        hip.run("vd_hallucinator_fwd_multi", hip.ptr(static), hip.ptr(dynamic), hip.ptr(sidx), hip.ptr(didx), hip.ptr(hidx),
+                hip.ptr(w), hip.ptr(b), n_hal, n, T, H, W, hip.ptr(out), st)
 
     def single():
-        hip.check(L.vd_hallucinator_fwd(hip.ptr(static), hip.ptr(dynamic), hip.ptr(sidx), hip.ptr(didx), hip.ptr(w), hip.ptr(b),
-                                        n, T, H, W, hip.ptr(out), st), "vd_hallucinator_fwd")
+        hip.run("vd_hallucinator_fwd", hip.ptr(static), hip.ptr(dynamic), hip.ptr(sidx), hip.ptr(didx), hip.ptr(w), hip.ptr(b), n,
+                T, H, W, hip.ptr(out), st)
     legs = {"vd_hallucinator_fwd": single, "vd_hallucinator_fwd_multi": multi}
     for fn in legs.values():
         for _ in range(5):

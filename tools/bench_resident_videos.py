@@ -105,18 +105,18 @@ def bench_kernels(D, dev, clips, launches, reps):
     out64 = torch.empty((clips, T, 3, 64, 64), dtype=torch.float32, device=dev)
     m = (ctypes.c_float * 3)(*D.IMAGENET_MEAN)
     s = (ctypes.c_float * 3)(*D.IMAGENET_STD)
-    L, st = hip.lib(), hip.stream_ptr(dev)
+    st = hip.stream_ptr(dev)
 
     def sample(flip):
-        return lambda: hip.check(L.vd_clips_sample(hip.ptr(store), ctypes.c_int64(store_frames), H, W, hip.ptr(rows), None, hip.ptr(flip),
-                                                   ctypes.c_int64(clips), T, H, W, hip.ptr(out), m, s, st), "vd_clips_sample")
+        return lambda: hip.run("vd_clips_sample", hip.ptr(store), store_frames, H, W, hip.ptr(rows), None, hip.ptr(flip), clips, T,
+                               H, W, hip.ptr(out), m, s, st)
 
     def sample_cropped():
-        hip.check(L.vd_clips_sample(hip.ptr(store100), ctypes.c_int64(nf), 100, 80, hip.ptr(rows100), hip.ptr(crops), hip.ptr(flips["half_flipped"]),
-                                    ctypes.c_int64(clips), T, 64, 64, hip.ptr(out64), m, s, st), "vd_clips_sample")
+        hip.run("vd_clips_sample", hip.ptr(store100), nf, 100, 80, hip.ptr(rows100), hip.ptr(crops), hip.ptr(flips["half_flipped"]),
+                clips, T, 64, 64, hip.ptr(out64), m, s, st)
 
     def normalise():
-        hip.check(L.vd_frames_normalize(hip.ptr(store), hip.ptr(out), ctypes.c_int64(nf), H, W, m, s, st), "vd_frames_normalize")
+        hip.run("vd_frames_normalize", hip.ptr(store), hip.ptr(out), nf, H, W, m, s, st)
 
     legs = {"frames_normalize": normalise, "clips_sample_cropped_100x80_to_64x64": sample_cropped}
     legs.update({"clips_sample_" + k: sample(v) for k, v in flips.items()})

@@ -1,7 +1,7 @@
 """Hallucinator backward (vd_hallucinator_bwd) against torch autograd of the same Conv3d on the GPU (a checker, not the product
 path) + its time, for the two forms: VD_HAL_FUSED=1 (default: one fused kernel) / 0 (data + parameter kernels).
 usage: python tools/hal_check.py [clips] [T] [H] [W]"""
-import os, sys, ctypes
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
@@ -22,11 +22,10 @@ st_r, dy_r, w_r, b_r = (t.clone().requires_grad_(True) for t in (stat, dyn, w, b
 x = torch.cat([st_r[sidx].unsqueeze(2).expand(-1, -1, T, -1, -1), dy_r[didx].permute(0, 2, 1, 3, 4)], 1)      # (n, 4, T, H, W)
 out = F.conv3d(x, w_r, b_r, padding=1)                                                                           # (n, 3, T, H, W)
 out.backward(go.permute(0, 2, 1, 3, 4))
-L = hip.lib()
 def run():
     g_dyn = torch.zeros_like(dyn); g_stat = torch.zeros_like(stat); g_w = torch.zeros_like(w); g_b = torch.zeros_like(b)
-    hip.check(L.vd_hallucinator_bwd(hip.ptr(go), hip.ptr(stat), hip.ptr(dyn), hip.ptr(sidx), hip.ptr(didx), hip.ptr(w), n, T, H, W,
-                                    hip.ptr(g_dyn), hip.ptr(g_stat), hip.ptr(g_w), hip.ptr(g_b), hip.stream_ptr("cuda")), "vd_hallucinator_bwd")
+    hip.run("vd_hallucinator_bwd", hip.ptr(go), hip.ptr(stat), hip.ptr(dyn), hip.ptr(sidx), hip.ptr(didx), hip.ptr(w), n, T, H, W,
+            hip.ptr(g_dyn), hip.ptr(g_stat), hip.ptr(g_w), hip.ptr(g_b), hip.stream_ptr("cuda"))
     return g_dyn, g_stat, g_w, g_b
 got = run()
 torch.cuda.synchronize()
@@ -38,8 +37,8 @@ for _ in range(8):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     g_dyn = torch.zeros_like(dyn); g_stat = torch.zeros_like(stat); g_w = torch.zeros_like(w); g_b = torch.zeros_like(b)
     e0.record()
-    L.vd_hallucinator_bwd(hip.ptr(go), hip.ptr(stat), hip.ptr(dyn), hip.ptr(sidx), hip.ptr(didx), hip.ptr(w), n, T, H, W,
-                          hip.ptr(g_dyn), hip.ptr(g_stat), hip.ptr(g_w), hip.ptr(g_b), hip.stream_ptr("cuda"))
+    hip.lib().vd_hallucinator_bwd(hip.ptr(go), hip.ptr(stat), hip.ptr(dyn), hip.ptr(sidx), hip.ptr(didx), hip.ptr(w), n, T, H, W,
+                                  hip.ptr(g_dyn), hip.ptr(g_stat), hip.ptr(g_w), hip.ptr(g_b), hip.stream_ptr("cuda"))
     e1.record(); torch.cuda.synchronize()
     ts.append(e0.elapsed_time(e1))
 ms = sorted(ts)[len(ts) // 2]

@@ -6,7 +6,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from video_distillation_amd import engine, plan, hip
-import ctypes
 nclips = int(sys.argv[1]) if len(sys.argv) > 1 else 3200
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 geo = plan.NetGeometry(16, 112, 112)
@@ -26,7 +25,7 @@ slots0 = torch.empty((1, n_slots0, 8), dtype=torch.int16, device="cuda")
 per = 64 * 16 * 3 * 112 * 15
 for k in range(0, nclips, 64):       # 64 distinct clips, repeated
     m = min(64, nclips - k)
-    L.vd_pix2rows(hip.ptr(x), None, ctypes.c_int64(m), 16, 112, 112, ctypes.c_void_p(slots0.data_ptr() + k // 64 * per * 16), None, e5.prec, st)
+    L.vd_pix2rows(hip.ptr(x), None, m, 16, 112, 112, slots0.data_ptr() + k // 64 * per * 16, None, e5.prec, st)
 n1 = nclips * int(np.prod(e5.fwd[0].plan.out_shape[:-1]))
 outs = {v: torch.empty((1, n1, 8), dtype=torch.int16, device="cuda") for v in engs}
 times = {v: [] for v in engs}

@@ -15,7 +15,7 @@ for shape, name in ((0, "v_mfma_f32_32x32x16_f16"), (1, "v_mfma_f32_16x16x32_f16
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(10):
-            hip.check(hip.lib().vd_mfma_peak(blocks, iters, shape, hip.ptr(out), hip.stream_ptr(dev)), "vd_mfma_peak")
+            hip.run("vd_mfma_peak", blocks, iters, shape, hip.ptr(out), hip.stream_ptr(dev))
         e1.record(); torch.cuda.synchronize()
         times.append(e0.elapsed_time(e1) / 10)
     tf = blocks * 4 * iters * 8 * 32768.0 / (min(times[-5:]) * 1e-3) / 1e12

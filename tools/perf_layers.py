@@ -3,7 +3,6 @@ import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from video_distillation_amd import engine, plan, hip
-import ctypes
 nclips = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 precs = sys.argv[2].split(",") if len(sys.argv) > 2 else ["f16", "f16x3"]
 geo = plan.NetGeometry(16, 112, 112)
@@ -42,7 +41,7 @@ for prec in precs:
         return a.elapsed_time(b)/reps
     w = eng._weights
     lo = slots0[1] if eng.planes == 2 else None
-    tp = t(lambda: L.vd_pix2rows(hip.ptr(x), None, ctypes.c_int64(nclips), 16, 112, 112, hip.ptr(slots0[0]), hip.ptr(lo), eng.prec, st))
+    tp = t(lambda: L.vd_pix2rows(hip.ptr(x), None, nclips, 16, 112, 112, hip.ptr(slots0[0]), hip.ptr(lo), eng.prec, st))
     t0 = t(lambda: eng.fwd[0].run(slots0, n_slots0, w[1], act1.data_ptr(), n1, None, nclips))
     t1 = t(lambda: eng.fwd[1].run(act1, n1, w[3], act2.data_ptr(), n2, None, nclips))
     t2 = t(lambda: eng.fwd[2].run(act2, n2, w[5], feats.data_ptr(), 0, None, nclips))

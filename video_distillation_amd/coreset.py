@@ -17,7 +17,6 @@ Ties go to the lowest index, as torch's ``argmin`` / ``argmax`` do.
 """
 from __future__ import annotations
 
-import ctypes
 import time
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -100,9 +99,8 @@ def select(features: torch.Tensor, counts, offsets, ipc: int, method: str, kcent
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
         cnt = torch.tensor(counts[c0:c1], dtype=torch.int32).to(dev)
         ofs = torch.tensor(offsets[c0:c1], dtype=torch.int64).to(dev)
-        hip.check(L.vd_coreset_select(hip.ptr(feats), D, hip.ptr(ofs), hip.ptr(cnt), c1 - c0, mc, int(ipc), code,
-                                      hip.ptr(out[c0 * ipc:]), hip.ptr(ws), ctypes.c_int64(nb), hip.stream_ptr(dev)),
-                  "vd_coreset_select")
+        hip.run("vd_coreset_select", hip.ptr(feats), D, hip.ptr(ofs), hip.ptr(cnt), c1 - c0, mc, int(ipc), code,
+                hip.ptr(out[c0 * ipc:]), hip.ptr(ws), nb, hip.stream_ptr(dev))
         c0 = c1
     return out
 

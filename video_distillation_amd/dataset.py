@@ -448,8 +448,7 @@ def frames_normalize(u8: torch.Tensor, out: torch.Tensor, mean: Sequence[float],
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
     with torch.cuda.device(u8.device):
-        hip.check(hip.lib().vd_frames_normalize(hip.ptr(u8), hip.ptr(out), ctypes.c_int64(n), int(h), int(w), m, s, hip.stream_ptr(u8.device)),
-                  "vd_frames_normalize")
+        hip.run("vd_frames_normalize", hip.ptr(u8), hip.ptr(out), n, int(h), int(w), m, s, hip.stream_ptr(u8.device))
     return out
 
 
@@ -628,10 +627,8 @@ def _sample_clips(frames, frame_row, flip, crop_yx, frames_per_clip, out_hw, mea
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
     with torch.cuda.device(frames.device):
-        hip.check(hip.lib().vd_clips_sample(hip.ptr(frames), ctypes.c_int64(store_frames), hs, ws, ctypes.c_void_p(base),
-                                            ctypes.c_void_p(base + o_crop if crops is not None else 0), ctypes.c_void_p(base + o_flip),
-                                            ctypes.c_int64(b), t, oh, ow, hip.ptr(out), m, s, hip.stream_ptr(frames.device)),
-                  "vd_clips_sample")
+        hip.run("vd_clips_sample", hip.ptr(frames), store_frames, hs, ws, base, (base + o_crop if crops is not None else 0),
+                base + o_flip, b, t, oh, ow, hip.ptr(out), m, s, hip.stream_ptr(frames.device))
     return out, (dev[o_extra:o_flip].view(torch.int64) if extra is not None else None)
 
 

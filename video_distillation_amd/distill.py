@@ -24,7 +24,6 @@ trainer logic with a CPU stand-in on ``gloo`` to check the sharding.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import collections
 import os
@@ -415,30 +414,26 @@ class HipBackend:
         loss = torch.empty(nclass, dtype=torch.float32, device=self.device)
         g = torch.empty_like(f_syn)
         hip = self.hip
-        hip.check(hip.lib().vd_dm_loss(hip.ptr(f_real), hip.ptr(f_syn), nclass, nreal, nsyn, dim, hip.ptr(loss),
-                                       hip.ptr(g), hip.stream_ptr(self.device)), "vd_dm_loss")
+        hip.run("vd_dm_loss", hip.ptr(f_real), hip.ptr(f_syn), nclass, nreal, nsyn, dim, hip.ptr(loss), hip.ptr(g),
+                hip.stream_ptr(self.device))
         return loss, g
 
     def group_sum(self, x: torch.Tensor, groups: int, per: int, scale: float) -> torch.Tensor:
         hip = self.hip
         out = torch.empty((groups, x.shape[1]), dtype=torch.float32, device=self.device)
-        hip.check(hip.lib().vd_group_sum(hip.ptr(x), groups, per, x.shape[1], ctypes.c_float(scale), hip.ptr(out),
-                                         hip.stream_ptr(self.device)), "vd_group_sum")
+        hip.run("vd_group_sum", hip.ptr(x), groups, per, x.shape[1], scale, hip.ptr(out), hip.stream_ptr(self.device))
         return out
 
     def sgd(self, x: torch.Tensor, buf: torch.Tensor, g: torch.Tensor, lr: float, mu: float, first: bool) -> None:
         hip = self.hip
-        hip.check(hip.lib().vd_sgd_momentum(hip.ptr(x), hip.ptr(buf), hip.ptr(g), ctypes.c_int64(x.numel()),
-                                            ctypes.c_float(lr), ctypes.c_float(mu), int(first),
-                                            hip.stream_ptr(self.device)), "vd_sgd_momentum")
+        hip.run("vd_sgd_momentum", hip.ptr(x), hip.ptr(buf), hip.ptr(g), x.numel(), lr, mu, int(first), hip.stream_ptr(self.device))
 
     def hallucinate(self, static, dynamic, sidx, didx, w, b):
         hip = self.hip
         n, T, H, W = int(sidx.numel()), dynamic.shape[-4], dynamic.shape[-2], dynamic.shape[-1]
         out = torch.empty((n, T, 3, H, W), dtype=torch.float32, device=self.device)
-        hip.check(hip.lib().vd_hallucinator_fwd(hip.ptr(static), hip.ptr(dynamic), hip.ptr(sidx), hip.ptr(didx),
-                                                hip.ptr(w), hip.ptr(b), n, T, H, W, hip.ptr(out),
-                                                hip.stream_ptr(self.device)), "vd_hallucinator_fwd")
+        hip.run("vd_hallucinator_fwd", hip.ptr(static), hip.ptr(dynamic), hip.ptr(sidx), hip.ptr(didx), hip.ptr(w), hip.ptr(b), n,
+                T, H, W, hip.ptr(out), hip.stream_ptr(self.device))
         return out
 
     def hallucinate_backward(self, g_out, static, dynamic, sidx, didx, w, need_static: bool):
@@ -448,10 +443,8 @@ class HipBackend:
         g_stat = torch.zeros_like(static) if need_static else None
         g_w = torch.zeros(324, dtype=torch.float32, device=self.device)
         g_b = torch.zeros(3, dtype=torch.float32, device=self.device)
-        hip.check(hip.lib().vd_hallucinator_bwd(hip.ptr(g_out), hip.ptr(static), hip.ptr(dynamic), hip.ptr(sidx),
-                                                hip.ptr(didx), hip.ptr(w), n, T, H, W, hip.ptr(g_dyn),
-                                                hip.ptr(g_stat), hip.ptr(g_w), hip.ptr(g_b),
-                                                hip.stream_ptr(self.device)), "vd_hallucinator_bwd")
+        hip.run("vd_hallucinator_bwd", hip.ptr(g_out), hip.ptr(static), hip.ptr(dynamic), hip.ptr(sidx), hip.ptr(didx), hip.ptr(w),
+                n, T, H, W, hip.ptr(g_dyn), hip.ptr(g_stat), hip.ptr(g_w), hip.ptr(g_b), hip.stream_ptr(self.device))
         return g_dyn, g_stat, g_w.view(3, 4, 3, 3, 3), g_b
 
 
@@ -1074,8 +1067,7 @@ class HipGMOps:
 
     def sgd(self, x, buf, g, lr, mu, first):
         hip = self.hip
-        hip.check(hip.lib().vd_sgd_momentum(hip.ptr(x), hip.ptr(buf), hip.ptr(g), ctypes.c_int64(x.numel()), ctypes.c_float(lr),
-                                            ctypes.c_float(mu), int(first), hip.stream_ptr(self.device)), "vd_sgd_momentum")
+        hip.run("vd_sgd_momentum", hip.ptr(x), hip.ptr(buf), hip.ptr(g), x.numel(), lr, mu, int(first), hip.stream_ptr(self.device))
 
     def train_epoch(self, net, images, labels, optimizer, batch_train: int):
         import types

@@ -110,9 +110,8 @@ class _DevPlan:
         if _PACK.queue is not None and self.n_w > 0:          # inside ``batched_packs()``: one launch for all of them at its exit
             _PACK.queue.append((w, self.widx, self.n_w, self.wpk[0], lo, self.prec))
             return
-        hip.check(hip.lib().vd_pack_weights(hip.ptr(w), hip.ptr(self.widx), ctypes.c_int64(self.n_w),
-                                            hip.ptr(self.wpk[0]), hip.ptr(lo), self.prec, hip.stream_ptr(w.device)),
-                  "vd_pack_weights")
+        hip.run("vd_pack_weights", hip.ptr(w), hip.ptr(self.widx), self.n_w, hip.ptr(self.wpk[0]), hip.ptr(lo), self.prec,
+                hip.stream_ptr(w.device))
 
     def pack_c8(self, w: torch.Tensor, scales: torch.Tensor) -> None:
         """Operand planes of a VD_PREC_F16C8 program (vd_pack_weights_c8): fp16 fragments + the fp8 fragments of W_hi and W_lo;
@@ -120,17 +119,16 @@ class _DevPlan:
         assert w.dtype == torch.float32 and w.is_contiguous() and self.wpk.shape[0] == 2
         pl = self.plan
         sets = self.n_w // (pl.CC * pl.S * pl.NT * 512)       # (position-tile programs: one operand set per box, chunk-major inside)
-        hip.check(hip.lib().vd_pack_weights_c8(hip.ptr(w), ctypes.c_int64(w.numel()), hip.ptr(self.widx), sets * pl.CC, pl.S, pl.NT,
-                                               hip.ptr(self.wpk[0]), hip.ptr(self.wpk[1]), hip.ptr(scales), hip.stream_ptr(w.device)),
-                  "vd_pack_weights_c8")
+        hip.run("vd_pack_weights_c8", hip.ptr(w), w.numel(), hip.ptr(self.widx), sets * pl.CC, pl.S, pl.NT, hip.ptr(self.wpk[0]),
+                hip.ptr(self.wpk[1]), hip.ptr(scales), hip.stream_ptr(w.device))
 
     def pack_dither(self, w: torch.Tensor, groups: int) -> None:
         """``groups`` dithered single-pass operand sets (vd_pack_weights_dither); ``run(..., group=g)`` multiplies by set g."""
         assert w.dtype == torch.float32 and w.is_contiguous() and self.wpk.shape[0] == 1
         if self.wpk_d is None or self.wpk_d.shape[0] != groups:
             self.wpk_d = torch.empty((groups, self.n_w), dtype=torch.int16, device=w.device)
-        hip.check(hip.lib().vd_pack_weights_dither(hip.ptr(w), hip.ptr(self.widx), ctypes.c_int64(self.n_w), int(groups),
-                                                   hip.ptr(self.wpk_d), self.prec, hip.stream_ptr(w.device)), "vd_pack_weights_dither")
+        hip.run("vd_pack_weights_dither", hip.ptr(w), hip.ptr(self.widx), self.n_w, int(groups), hip.ptr(self.wpk_d), self.prec,
+                hip.stream_ptr(w.device))
 
     def run(self, src: torch.Tensor, src_plane_slots: int, bias: Optional[torch.Tensor], dst_ptr: int,
             dst_plane_stride: int, argmax: Optional[torch.Tensor], nclips: int, out_scale: Optional[torch.Tensor] = None,
@@ -174,11 +172,11 @@ class _DevPlan:
             if self.breg_variant == 4:
                 p.persist = persist | 0x80000          # (VdConvParams.persist bit 19: the plain K loop on a frame-tile program)
             try:
-                hip.check(hip.lib().vd_conv0_breg(ctypes.byref(p), hip.stream_ptr(src.device)), "vd_conv0_breg(%s)" % self.plan.name)
+                hip.run("vd_conv0_breg", ctypes.byref(p), hip.stream_ptr(src.device), what="vd_conv0_breg(%s)" % self.plan.name)
             finally:
                 p.persist = persist
         else:
-            hip.check(hip.lib().vd_conv_mfma(ctypes.byref(p), hip.stream_ptr(src.device)), "vd_conv_mfma(%s)" % self.plan.name)
+            hip.run("vd_conv_mfma", ctypes.byref(p), hip.stream_ptr(src.device), what="vd_conv_mfma(%s)" % self.plan.name)
         if prof is not None:
             e1.record()
             prof.append((self.plan.name, self.prec, 2.0 * self.plan.meta.get("macs_per_unit", 0) * nclips, e0, e1))
@@ -232,7 +230,7 @@ def flush_packs(q) -> None:
             sg = b.seg[k]
             sg.w, sg.widx, sg.n = w.data_ptr(), widx.data_ptr(), int(n)
             sg.out_hi, sg.out_lo, sg.prec = hi.data_ptr(), (0 if lo is None else lo.data_ptr()), int(prec)
-        hip.check(hip.lib().vd_pack_weights_multi(ctypes.byref(b), hip.stream_ptr(part[0][0].device)), "vd_pack_weights_multi")
+        hip.run("vd_pack_weights_multi", ctypes.byref(b), hip.stream_ptr(part[0][0].device))
 
 
 def run_together(plans: Sequence["_DevPlan"], *args, **kwargs) -> None:
@@ -267,8 +265,8 @@ def run_together(plans: Sequence["_DevPlan"], *args, **kwargs) -> None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
             dev = part[0].tables.device
-            hip.check(hip.lib().vd_conv_mfma_multi(arr, len(part), hip.stream_ptr(dev)),
-                      "vd_conv_mfma_multi(%s)" % ",".join(dp.plan.name for dp in part))
+            hip.run("vd_conv_mfma_multi", arr, len(part), hip.stream_ptr(dev),
+                    what="vd_conv_mfma_multi(%s)" % ",".join(dp.plan.name for dp in part))
             if prof is not None:
                 e1.record()
                 nclips = int(part[0].params.nclips)
@@ -297,13 +295,12 @@ def round_weights(params: Sequence[torch.Tensor], prec: str, levels: Sequence[in
     weights in every pass: it is the exact step of the network rn16(W), so weight rounding cannot appear as a
     bias between mean f_real and mean f_syn (that bias is what grows, relative to the gradient, as the
     distillation converges and the difference of the means shrinks)."""
-    out, L = [], hip.lib()
+    out = []
     for i, p in enumerate(params):
         if i % 2 == 0 and p.dim() == 5 and i < 6 and (i // 2) in levels:     # (``levels``: conv levels whose weights are rounded)
             p = p.detach().to(torch.float32).contiguous()
             q = torch.empty_like(p)
-            hip.check(L.vd_round_operand(hip.ptr(p), ctypes.c_int64(p.numel()), hip.PREC[prec], hip.ptr(q),
-                                         hip.stream_ptr(p.device)), "vd_round_operand")
+            hip.run("vd_round_operand", hip.ptr(p), p.numel(), hip.PREC[prec], hip.ptr(q), hip.stream_ptr(p.device))
             out.append(q)
         else:
             out.append(p)
@@ -468,12 +465,12 @@ class EmbedEngine:
         rowp = P.pix_row_pitch(g.width)
         per = g.frames * 3 * g.height * (rowp // 8)
         rows = torch.empty((self.planes, N * per, 8), dtype=torch.int16, device=self.device)
-        L, st = hip.lib(), hip.stream_ptr(self.device)
+        st = hip.stream_ptr(self.device)
         for i in range(0, N, step):
             nb = min(step, N - i)
             lo = rows[1, i * per:] if self.planes == 2 else None
-            hip.check(L.vd_pix2rows(hip.ptr(pool[i:]), hip.ptr(None), ctypes.c_int64(nb), g.frames, g.height, g.width,
-                                     hip.ptr(rows[0, i * per:]), hip.ptr(lo), self.prec, st), "vd_pix2rows")
+            hip.run("vd_pix2rows", hip.ptr(pool[i:]), hip.ptr(None), nb, g.frames, g.height, g.width, hip.ptr(rows[0, i * per:]),
+                    hip.ptr(lo), self.prec, st)
         return rows
 
     def forward(self, x: torch.Tensor, keep: bool = False, index: Optional[torch.Tensor] = None,
@@ -492,7 +489,6 @@ class EmbedEngine:
             index = index.to(self.device, torch.int64).contiguous()
         feats = torch.empty((B, self.num_feat), dtype=torch.float32, device=self.device)
         saved = []
-        L = hip.lib()
         st = hip.stream_ptr(self.device)
         rowp = P.pix_row_pitch(g.width)
         per1 = int(np.prod(self.fwd[0].plan.out_shape[:-1]))
@@ -508,9 +504,8 @@ class EmbedEngine:
                 slots0 = self._buf("slots0", (self.planes, n_slots0, 8), torch.int16)
                 lo = slots0[1] if self.planes == 2 else None
                 xin = x[c0:] if index is None else x
-                hip.check(L.vd_pix2rows(hip.ptr(xin), hip.ptr(None if index is None else index[c0:]),
-                                         ctypes.c_int64(nb), g.frames, g.height, g.width,
-                                         hip.ptr(slots0[0]), hip.ptr(lo), self.prec, st), "vd_pix2rows")
+                hip.run("vd_pix2rows", hip.ptr(xin), hip.ptr(None if index is None else index[c0:]), nb, g.frames, g.height,
+                        g.width, hip.ptr(slots0[0]), hip.ptr(lo), self.prec, st)
             n1, n2 = nb * per1, nb * per2
             hilo = self.fwd2x is not None
             assert not (hilo and keep), "last_hilo engines have no kept-arg-max forward"
@@ -565,9 +560,8 @@ class EmbedEngine:
         if rows is None:
             n_slots0 = B * g.frames * 3 * g.height * (rowp // 8)
             slots0 = self._buf("slots0", (1, n_slots0, 8), torch.int16)
-            hip.check(hip.lib().vd_pix2rows(hip.ptr(x.detach().to(torch.float32).contiguous()), hip.ptr(index), ctypes.c_int64(B),
-                                            g.frames, g.height, g.width, hip.ptr(slots0[0]), hip.ptr(None), self.prec,
-                                            hip.stream_ptr(self.device)), "vd_pix2rows")
+            hip.run("vd_pix2rows", hip.ptr(x.detach().to(torch.float32).contiguous()), hip.ptr(index), B, g.frames, g.height,
+                    g.width, hip.ptr(slots0[0]), hip.ptr(None), self.prec, hip.stream_ptr(self.device))
         if self.fwd[0].breg_ok:       # register-resident-B kernel: reloads its fragments when a workgroup's walk crosses into the next set
             if rows is not None:
                 self.fwd[0].run(rows, int(rows.shape[1]), w[1], act1.data_ptr(), n1, None, B, clip_index=index, set_clips=per)
@@ -607,7 +601,6 @@ class EmbedEngine:
         g_feat = g_feat.detach().to(torch.float32).contiguous()
         B = g_feat.shape[0]
         dx = torch.empty((B, g.frames, g.channel, g.height, g.width), dtype=torch.float32, device=self.device)
-        L = hip.lib()
         st = hip.stream_ptr(self.device)
         for c0, nb, am0, am1, am2 in saved:
             grad = g_feat[c0:c0 + nb]
@@ -623,12 +616,10 @@ class EmbedEngine:
                     # exponent range with an exact power-of-two scale (DM gradients shrink by orders of
                     # magnitude per layer and would otherwise fall into fp16's subnormals)
                     scb = self._buf("gscale%d" % li, (4,), torch.float32)
-                    hip.check(L.vd_absmax_scale(hip.ptr(grad), ctypes.c_int64(grad.numel()), ctypes.c_float(GRAD_TARGET()),
-                                                hip.ptr(scb), st), "vd_absmax_scale")
+                    hip.run("vd_absmax_scale", hip.ptr(grad), grad.numel(), GRAD_TARGET(), hip.ptr(scb), st)
                     sc, inv = scb, scb[1:]
-                hip.check(L.vd_unpool_relu_bwd(hip.ptr(grad), hip.ptr(am), ctypes.c_int64(nb), cout, To, Ho, Wo, pt,
-                                               T, OH, OW, layout, hip.ptr(dy[0]), hip.ptr(lo), self.prec_bwd, hip.ptr(sc), st),
-                          "vd_unpool_relu_bwd")
+                hip.run("vd_unpool_relu_bwd", hip.ptr(grad), hip.ptr(am), nb, cout, To, Ho, Wo, pt, T, OH, OW, layout,
+                        hip.ptr(dy[0]), hip.ptr(lo), self.prec_bwd, hip.ptr(sc), st)
                 if lo is not None and os.environ.get("VD_BWD_X2_SIM") == "g":
                     lo.zero_()      # measurement knob: the numerics of g_hi x (W_hi + W_lo)
                 if li == 0:
@@ -667,36 +658,35 @@ class WgradOp:
         self.rep = torch.empty((self.replicas, cin * 147, cout), dtype=torch.float32, device=self.device)
 
     def _stage_x(self, x_src: torch.Tensor, x_is_pixels: bool, x_plane_slots: int) -> None:
-        L, st = hip.lib(), hip.stream_ptr(self.device)
+        st = hip.stream_ptr(self.device)
         nb = self.nclips
         if x_is_pixels:
             lo = self.xT[1] if self.planes == 2 else None
-            hip.check(L.vd_clip_minor_pix(hip.ptr(x_src), ctypes.c_int64(nb), self.t, self.h, self.w, hip.ptr(self.xT[0]),
-                                          hip.ptr(lo), self.prec, st), "vd_clip_minor_pix")
+            hip.run("vd_clip_minor_pix", hip.ptr(x_src), nb, self.t, self.h, self.w, hip.ptr(self.xT[0]), hip.ptr(lo), self.prec,
+                    st)
         else:
-            hip.check(L.vd_clip_minor_cl(hip.ptr(x_src), ctypes.c_int64(x_plane_slots), self.planes, ctypes.c_int64(nb), self.cin,
-                                         ctypes.c_int64(self.npos_in), hip.ptr(self.xT), ctypes.c_int64(self.xT.shape[1]), st),
-                      "vd_clip_minor_cl")
+            hip.run("vd_clip_minor_cl", hip.ptr(x_src), x_plane_slots, self.planes, nb, self.cin, self.npos_in, hip.ptr(self.xT),
+                    self.xT.shape[1], st)
 
     def _accumulate(self, dw_out: torch.Tensor, out_scale: Optional[torch.Tensor]) -> None:
         """The tile program over the staged x and the packed dy: boxes accumulate into `replicas` cout-minor copies
         (coalesced atomics, no same-address pile-up), which are then folded into dw_out."""
-        L, st = hip.lib(), hip.stream_ptr(self.device)
+        st = hip.stream_ptr(self.device)
         self.rep.zero_()
         self.dp.params.replica_stride = dw_out.numel()
         self.dp.run(self.xT, self.xT.shape[1], None, self.rep.data_ptr(), 0, None, self.cin, out_scale=out_scale, wpk=self.bp,
                     w_plane_elems=self.bp_elems)
-        hip.check(L.vd_replica_sum(hip.ptr(self.rep), self.replicas, self.cin * 147, self.cout, hip.ptr(dw_out), st), "vd_replica_sum")
+        hip.run("vd_replica_sum", hip.ptr(self.rep), self.replicas, self.cin * 147, self.cout, hip.ptr(dw_out), st)
 
     def run(self, x_src: torch.Tensor, x_is_pixels: bool, x_plane_slots: int, dy: torch.Tensor, dy_plane_slots: int,
             dw_out: torch.Tensor, out_scale: Optional[torch.Tensor] = None) -> None:
         """x_src: fp32 clips (B,T,3,H,W) if x_is_pixels else channels-last slots [planes][clip][C/8][npos][8];
         dy: dense slots [planes][clip][N/8][T][OH][OW][8]; dw_out (cout,cin,3,7,7) fp32 is ACCUMULATED into."""
-        L, st = hip.lib(), hip.stream_ptr(self.device)
+        st = hip.stream_ptr(self.device)
         self._stage_x(x_src, x_is_pixels, x_plane_slots)
         nt, noh, now = self.plan.meta["box"]
-        hip.check(L.vd_pack_dy(hip.ptr(dy), ctypes.c_int64(dy_plane_slots), self.planes, ctypes.c_int64(self.nclips), self.cout, self.T,
-                               self.OH, self.OW, nt, noh, now, hip.ptr(self.bp), ctypes.c_int64(self.bp_elems), st), "vd_pack_dy")
+        hip.run("vd_pack_dy", hip.ptr(dy), dy_plane_slots, self.planes, self.nclips, self.cout, self.T, self.OH, self.OW, nt, noh,
+                now, hip.ptr(self.bp), self.bp_elems, st)
         self._accumulate(dw_out, out_scale)
 
     def run_pooled(self, x_src: torch.Tensor, x_is_pixels: bool, x_plane_slots: int, g_pooled: torch.Tensor, argmax: torch.Tensor,
@@ -705,12 +695,11 @@ class WgradOp:
         """As ``run`` for a layer whose dense dy has no other reader: dy = backward of ReLU + max-pool of the POOLED gradient
         ``g_pooled`` (layout / arg-max bytes as vd_unpool_relu_bwd takes them; ``pooled`` = (To, Ho, Wo, pool_t)) goes
         straight into the packed B operand (vd_unpool_relu_bwd_packed), bitwise what unpool + pack produce."""
-        L, st = hip.lib(), hip.stream_ptr(self.device)
+        st = hip.stream_ptr(self.device)
         self._stage_x(x_src, x_is_pixels, x_plane_slots)
         nt, noh, now = self.plan.meta["box"]
         To, Ho, Wo, pt = pooled
         lo = self.bp[1] if self.planes == 2 else None
-        hip.check(L.vd_unpool_relu_bwd_packed(hip.ptr(g_pooled), hip.ptr(argmax), ctypes.c_int64(self.nclips), self.cout, To, Ho, Wo, pt,
-                                              self.T, self.OH, self.OW, g_layout, nt, noh, now, hip.ptr(self.bp[0]), hip.ptr(lo),
-                                              self.prec, hip.ptr(scale), st), "vd_unpool_relu_bwd_packed")
+        hip.run("vd_unpool_relu_bwd_packed", hip.ptr(g_pooled), hip.ptr(argmax), self.nclips, self.cout, To, Ho, Wo, pt, self.T,
+                self.OH, self.OW, g_layout, nt, noh, now, hip.ptr(self.bp[0]), hip.ptr(lo), self.prec, hip.ptr(scale), st)
         self._accumulate(dw_out, out_scale)

@@ -1,4 +1,5 @@
-"""ctypes binding of libvd_hip.so (C ABI declared in include/vd_hip.h).
+"""ctypes binding of libvd_hip.so.  include/vd_hip.h is the one declaration of its C ABI: every entry point's ``restype`` and
+``argtypes`` are parsed from it (``bind``), call sites pass plain Python values, a wrong count or type raises before the call.
 
 PyTorch is used only as the owner of device memory and streams: every call passes
 ``tensor.data_ptr()`` and the current HIP stream handle.  There is deliberately NO fallback:
@@ -7,7 +8,9 @@ if the shared library is missing or a kernel launch fails, a RuntimeError is rai
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
+import re
 import subprocess
 from typing import Optional
 
@@ -23,18 +26,6 @@ HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
-EXPORTS = ("vd_abi_version", "vd_conv_mfma", "vd_conv_mfma_multi", "vd_conv0_breg", "vd_pack_weights", "vd_round_operand", "vd_pix2rows", "vd_unpool_relu_bwd", "vd_absmax_scale", "vd_dm_loss",
-           "vd_group_sum", "vd_sgd_momentum", "vd_hallucinator_fwd", "vd_hallucinator_bwd", "vd_match_rows_fwd", "vd_match_rows_bwd", "vd_match_rows_fwd_multi", "vd_match_rows_bwd_multi", "vd_head_fwd", "vd_clip_minor_cl", "vd_clip_minor_pix", "vd_pack_dy", "vd_bias_grad", "vd_bias_grad_pooled", "vd_standardize", "vd_head_train_fwd", "vd_ce_loss", "vd_head_train_bwd", "vd_head_second_order", "vd_resplit_slots", "vd_program_load", "vd_program_pack_weights",
-           "vd_program_run", "vd_program_info", "vd_program_free",
-           "vd_sgd_momentum_wd", "vd_frames_normalize", "vd_replica_sum", "vd_pack_weights_dither", "vd_unpool_relu_bwd_packed", "vd_mfma_peak", "vd_program_build", "vd_program_build_dgrad", "vd_program_build_wgrad", "vd_program_run_wgrad", "vd_train_create", "vd_train_workspace_bytes", "vd_train_step", "vd_train_free", "vd_blob_free", "vd_embed_create", "vd_embed_create_ex", "vd_embed_argmax_bytes", "vd_embed_backward_workspace_bytes",
-           "vd_embed_forward_keep", "vd_embed_backward", "vd_program_run_scaled", "vd_embed_num_features",
-           "vd_embed_workspace_bytes", "vd_embed_set_weights", "vd_embed_forward", "vd_embed_free",
-           "vd_comm_unique_id", "vd_comm_create", "vd_comm_size", "vd_comm_version", "vd_comm_rank", "vd_comm_allreduce_f32", "vd_comm_allgather_f32",
-           "vd_comm_free",
-           "vd_bias_grad_pooled_scratch_floats", "vd_bias_grad_pooled_ordered", "vd_standardize_ordered", "vd_head_train_bwd_ordered",
-           "vd_set_deterministic", "vd_get_deterministic", "vd_pack_weights_c8", "vd_pack_weights_multi",
-           "vd_split_scaled", "vd_scale_combine", "vd_sources_hash", "vd_coreset_workspace_bytes", "vd_coreset_select",
-           "vd_clips_sample", "vd_eval_stats", "vd_hallucinator_fwd_multi")
 F16X3_WSHIFT = 8          # include/vd_hip.h VD_F16X3_WSHIFT: packed fp16 hi+lo weights are W x 2^8, undone in the programs' epilogues
 
 
@@ -76,8 +67,11 @@ class VdPackBatch(ctypes.Structure):
     _fields_ = [("nseg", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seg", VdPackSeg * VD_PACK_MAX)]
 
 
+VD_MATCH_MAX_SEG = 16
+
+
 class VdMatchBatch(ctypes.Structure):
-    _fields_ = [("nseg", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seg", VdMatchSeg * 16)]
+    _fields_ = [("nseg", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seg", VdMatchSeg * VD_MATCH_MAX_SEG)]
 
 
 def build(force: bool = False, verbose: bool = False, debug_hooks: bool = False) -> str:
@@ -182,6 +176,66 @@ def sources_hash() -> str:
     return h.hexdigest()[:16]
 
 
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
+_RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None, "const char*": ctypes.c_char_p}
+_PROTOTYPE = re.compile(r"(int64_t|int|void|const char\s*\*)\s*(vd_[a-z0-9_]+)\s*\(([^()]*)\)")
+_PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+")
+
+
+def parse_header(text: str) -> dict:
+    """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses -> {name: (restype, [argtypes])}.  Anything
+    else -- a type outside the set, a statement that is not wholly a prototype -- is a ``ValueError`` that quotes it; no guesses."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"typedef\s+struct\s*\w*\s*(\{[^{}]*\}\s*)?\w+\s*;", " ", text)
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|^[ \t]*\}[ \t]*$', " ", text, flags=re.M)      # (no directive is continued)
+    sigs = {}
+    for stmt in filter(None, (" ".join(part.split()) for part in text.split(";"))):
+        m = _PROTOTYPE.fullmatch(stmt)
+        if m is None or m.group(2) in sigs:
+            raise ValueError("include/vd_hip.h: not a prototype the binding understands, or a second one of its name: %r" % stmt)
+        ret, name, params = m.group(1).replace(" *", "*"), m.group(2), m.group(3).strip()
+        argtypes = []
+        for par in ([] if params == "void" else params.split(",")):
+            pm = _PARAMETER.fullmatch(par.strip())
+            if pm is None or not (pm.group(2) or pm.group(1) in _SCALARS):
+                raise ValueError("include/vd_hip.h: parameter %r of %r has no ctypes mapping" % (par.strip(), stmt))
+            argtypes.append(ctypes.c_void_p if pm.group(2) else _SCALARS[pm.group(1)])
+        sigs[name] = (_RETURNS[ret], argtypes)
+    return sigs
+
+
+@functools.lru_cache(maxsize=None)
+def signatures() -> dict:
+    """{name: (restype, [argtypes])} of include/vd_hip.h, read and parsed once, when first asked for (binding a library does)."""
+    with open(HEADER) as f:
+        return parse_header(f.read())
+
+
+def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
+    if name == "EXPORTS":
+        return tuple(signatures())
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+class _Library(ctypes.CDLL):
+    # ctypes lets a cdecl function take MORE arguments than its argtypes (C varargs); without FUNCFLAG_CDECL the count has to be
+    # exact, and the flag selects another calling convention on 32-bit Windows only.  That is how CPython reads the flag, not
+    # documented behaviour: tests/test_cabi.py::test_wrong_arguments_are_exceptions_before_the_call guards it
+    _func_flags_ = 0
+
+
+def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
+    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h."""
+    L = _Library(path)
+    for name, (restype, argtypes) in signatures().items():
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        elif not allow_missing:
+            raise RuntimeError("libvd_hip.so does not export %s" % name)
+    return L
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -208,28 +262,16 @@ def lib() -> ctypes.CDLL:
                 if library_stamp(path) != want:
                     raise RuntimeError("libvd_hip.so at %s carries stamp %s, the checkout's kernel sources hash to %s"
                                        % (path, library_stamp(path), want))
-        L = ctypes.CDLL(path)
-        for name in EXPORTS:
-            if not hasattr(L, name):
-                if "VD_LIB_PATH" in os.environ:      # an older build loaded on purpose for an A/B measurement
-                    continue
-                raise RuntimeError("libvd_hip.so does not export %s" % name)
-            getattr(L, name).restype = {"vd_program_info": ctypes.c_int64, "vd_program_free": None, "vd_blob_free": None, "vd_embed_free": None, "vd_train_free": None, "vd_comm_free": None, "vd_train_workspace_bytes": ctypes.c_int64, "vd_bias_grad_pooled_scratch_floats": ctypes.c_int64,
-                                        "vd_embed_num_features": ctypes.c_int64, "vd_embed_workspace_bytes": ctypes.c_int64,
-                                        "vd_embed_argmax_bytes": ctypes.c_int64, "vd_embed_backward_workspace_bytes": ctypes.c_int64,
-                                        "vd_coreset_workspace_bytes": ctypes.c_int64}.get(name, ctypes.c_int)
+        L = bind(path, allow_missing="VD_LIB_PATH" in os.environ)      # (an older build loaded on purpose for an A/B measurement)
         if L.vd_abi_version() != 5:
             raise RuntimeError("libvd_hip.so ABI version mismatch")
-        if hasattr(L, "vd_sources_hash"):
-            L.vd_sources_hash.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
 
 def loaded_stamp() -> str:
     """Sources hash compiled into the library this process runs on (bench.py and smoke() print it)."""
-    v = lib().vd_sources_hash()
-    v = v.decode() if isinstance(v, bytes) else str(v)
+    v = lib().vd_sources_hash().decode()
     return v[len(STAMP_PREFIX):] if v.startswith(STAMP_PREFIX) else v
 
 
@@ -244,8 +286,8 @@ def set_deterministic(on: bool) -> bool:
     return bool(lib().vd_set_deterministic(int(bool(on))))
 
 
-def stream_ptr(device=None) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+def stream_ptr(device=None) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 def check(code: int, what: str) -> None:
@@ -253,8 +295,13 @@ def check(code: int, what: str) -> None:
         raise RuntimeError("%s failed with code %d" % (what, code))
 
 
-def ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+def run(name: str, *args, what: Optional[str] = None) -> None:
+    """Call entry point ``name`` and raise on a non-zero code (``what``: its name in the message where that says more)."""
+    check(getattr(lib(), name)(*args), what or name)
+
+
+def ptr(t: Optional[torch.Tensor]) -> int:
+    return 0 if t is None else t.data_ptr()
 
 
 def is_x3(prec: int) -> bool:
@@ -285,7 +332,7 @@ def eval_stats(logits: torch.Tensor, labels: torch.Tensor, rec: torch.Tensor) ->
     z = logits.detach().to(torch.float32).contiguous()
     y = labels.detach().to(torch.int64).contiguous()
     if z.is_cuda:
-        check(lib().vd_eval_stats(ptr(z), ptr(y), B, K, ptr(rec), stream_ptr(z.device)), "vd_eval_stats")
+        run("vd_eval_stats", ptr(z), ptr(y), B, K, ptr(rec), stream_ptr(z.device))
         return rec
     if B == 0:
         return rec
@@ -369,9 +416,8 @@ def hallucinate_multi(static: torch.Tensor, dynamic: torch.Tensor, sidx, didx, h
     tab = host.to(dev, non_blocking=True)
     base = tab.data_ptr()
     with torch.cuda.device(dev):
-        check(lib().vd_hallucinator_fwd_multi(ptr(static), ptr(dynamic), ctypes.c_void_p(base), ctypes.c_void_p(base + o_d),
-                                              ctypes.c_void_p(base + o_h), ptr(weights), ptr(biases), nh, n, T, H, W, ptr(out),
-                                              stream_ptr(dev)), "vd_hallucinator_fwd_multi")
+        run("vd_hallucinator_fwd_multi", ptr(static), ptr(dynamic), base, base + o_d, base + o_h, ptr(weights), ptr(biases), nh, n,
+            T, H, W, ptr(out), stream_ptr(dev))
     return out if e is None else (out, tab[o_e:o_h].view(torch.int64))
 
 
@@ -383,16 +429,15 @@ class Comm:
 
     def __init__(self, rank: int, world: int):
         import torch.distributed as dist
-        L = lib()
         ident = (ctypes.c_char * 128)()
         if rank == 0:
-            check(L.vd_comm_unique_id(ident), "vd_comm_unique_id")
+            run("vd_comm_unique_id", ident)
         if world > 1:
             box = [bytes(ident)]
             dist.broadcast_object_list(box, src=0)
             ident = (ctypes.c_char * 128).from_buffer_copy(box[0])
         self._c = ctypes.c_void_p()
-        check(L.vd_comm_create(ident, world, rank, ctypes.byref(self._c)), "vd_comm_create")
+        run("vd_comm_create", ident, world, rank, ctypes.byref(self._c))
         self.rank, self.world = rank, world
 
     def size(self) -> int:
@@ -405,7 +450,7 @@ class Comm:
 
     def all_reduce(self, t: torch.Tensor) -> None:
         assert t.dtype == torch.float32 and t.is_contiguous()
-        check(lib().vd_comm_allreduce_f32(self._c, ptr(t), ptr(t), ctypes.c_int64(t.numel()), stream_ptr(t.device)), "vd_comm_allreduce_f32")
+        run("vd_comm_allreduce_f32", self._c, ptr(t), ptr(t), t.numel(), stream_ptr(t.device))
 
     def free(self) -> None:
         if self._c:

@@ -410,7 +410,6 @@ class ConvNet3D(nn.Module):
         """Inference logits on the HIP path: MFMA features + fused head kernel (avg-pool, 1x1x1
         conv, max over T).  Used whenever no gradient is being recorded (evaluate_synset's three
         test passes per evaluation, utils.py:793-824)."""
-        import ctypes
         from . import hip
         feats = _EmbedFunction.apply(x.detach(), self, False)      # inference: plain rn16 weights, one launch per layer
         g = P.NetGeometry(x.shape[1], x.shape[3], x.shape[4])
@@ -421,8 +420,8 @@ class ConvNet3D(nn.Module):
         w = self.logit.weight.detach().reshape(K, C).float().contiguous()
         b = self.logit.bias.detach().float().contiguous()
         out = torch.empty((x.shape[0], K), dtype=torch.float32, device=x.device)
-        hip.check(hip.lib().vd_head_fwd(hip.ptr(feats), hip.ptr(w), hip.ptr(b), ctypes.c_int64(x.shape[0]), C, To, Ho, Wo,
-                                        kt, kh, kw, K, hip.ptr(out), hip.stream_ptr(x.device)), "vd_head_fwd")
+        hip.run("vd_head_fwd", hip.ptr(feats), hip.ptr(w), hip.ptr(b), x.shape[0], C, To, Ho, Wo, kt, kh, kw, K, hip.ptr(out),
+                hip.stream_ptr(x.device))
         return out
 
     # -- training step on the HIP path (utils.epoch 'train' dispatches here) ----------------------

@@ -13,7 +13,6 @@ is the module-level entry ``utils.epoch`` dispatches to.  No CPU path.
 from __future__ import annotations
 
 import contextlib
-import ctypes
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -34,12 +33,10 @@ def standardize(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(x)
     if hip.deterministic():         # fixed summation order: per-block partial sums, folded identically by every block
         scratch = torch.empty(4096, dtype=torch.float64, device=x.device)
-        hip.check(hip.lib().vd_standardize_ordered(hip.ptr(x), ctypes.c_int64(x.numel()), hip.ptr(scratch), hip.ptr(out),
-                                                   hip.stream_ptr(x.device)), "vd_standardize_ordered")
+        hip.run("vd_standardize_ordered", hip.ptr(x), x.numel(), hip.ptr(scratch), hip.ptr(out), hip.stream_ptr(x.device))
         return out
     scratch = torch.empty(2, dtype=torch.float64, device=x.device)
-    hip.check(hip.lib().vd_standardize(hip.ptr(x), ctypes.c_int64(x.numel()), hip.ptr(scratch), hip.ptr(out),
-                                       hip.stream_ptr(x.device)), "vd_standardize")
+    hip.run("vd_standardize", hip.ptr(x), x.numel(), hip.ptr(scratch), hip.ptr(out), hip.stream_ptr(x.device))
     return out
 
 
@@ -101,7 +98,7 @@ class TrainEngine:
     def head_forward(self, feats: torch.Tensor, mask: Optional[torch.Tensor], w: torch.Tensor, b: torch.Tensor) -> dict:
         """AvgPool3d -> dropout mask -> 1x1x1 conv -> max over frames (networks.py:741-745) of (B, num_feat) features.
         Returns the head state {logits, dropped, amt, mask, wl, bl}."""
-        L, st = hip.lib(), hip.stream_ptr(self.device)
+        st = hip.stream_ptr(self.device)
         B = int(feats.shape[0])
         wl = w.detach().reshape(self.K, self.C).to(torch.float32).contiguous()
         bl = b.detach().to(torch.float32).contiguous()
@@ -112,22 +109,20 @@ class TrainEngine:
         if mask is not None:
             mask = mask.to(self.device, torch.float32).contiguous()
             assert tuple(mask.shape) == (B, self.C, self.Tp), mask.shape
-        hip.check(L.vd_head_train_fwd(hip.ptr(feats), hip.ptr(mask), hip.ptr(wl), hip.ptr(bl), ctypes.c_int64(B), self.C,
-                                      self.To, self.Ho, self.Wo, kt, kh, kw, self.K, hip.ptr(dropped), hip.ptr(logits),
-                                      hip.ptr(amt), st), "vd_head_train_fwd")
+        hip.run("vd_head_train_fwd", hip.ptr(feats), hip.ptr(mask), hip.ptr(wl), hip.ptr(bl), B, self.C, self.To, self.Ho, self.Wo,
+                kt, kh, kw, self.K, hip.ptr(dropped), hip.ptr(logits), hip.ptr(amt), st)
         return dict(logits=logits, dropped=dropped, amt=amt, mask=mask, wl=wl, bl=bl)
 
     def head_backward(self, hs: dict, dlog: torch.Tensor, g_w: torch.Tensor, g_b: torch.Tensor) -> torch.Tensor:
         """Backward of ``head_forward`` for the logit gradient ``dlog`` (B,K): accumulates into g_w / g_b (zeroed by the
         caller), returns the feature gradient (B, num_feat)."""
-        L, st = hip.lib(), hip.stream_ptr(self.device)
+        st = hip.stream_ptr(self.device)
         B = int(dlog.shape[0])
         kt, kh, kw = self.pool_kernel
         g_feat = torch.empty((B, self.eng.num_feat), dtype=torch.float32, device=self.device)
-        fn = L.vd_head_train_bwd_ordered if hip.deterministic() else L.vd_head_train_bwd
-        hip.check(fn(hip.ptr(dlog), hip.ptr(hs["amt"]), hip.ptr(hs["dropped"]), hip.ptr(hs["mask"]),
-                     hip.ptr(hs["wl"]), ctypes.c_int64(B), self.C, self.To, self.Ho, self.Wo, kt, kh, kw,
-                     self.K, hip.ptr(g_w), hip.ptr(g_b), hip.ptr(g_feat), st), "vd_head_train_bwd")
+        hip.run("vd_head_train_bwd_ordered" if hip.deterministic() else "vd_head_train_bwd", hip.ptr(dlog), hip.ptr(hs["amt"]),
+                hip.ptr(hs["dropped"]), hip.ptr(hs["mask"]), hip.ptr(hs["wl"]), B, self.C, self.To, self.Ho, self.Wo, kt, kh, kw,
+                self.K, hip.ptr(g_w), hip.ptr(g_b), hip.ptr(g_feat), st, what="vd_head_train_bwd")
         return g_feat
 
     def feat_backward(self, x: torch.Tensor, nb: int, am, g_feat: torch.Tensor, g: Optional[Sequence[torch.Tensor]],
@@ -138,7 +133,7 @@ class TrainEngine:
         engine's weights / packed dgrad operands must be current; activations are read from the engine workspace.
         ``keep_dense``: a second-order sweep will read the first layer's dense gradient slots (workspace ``dy0``); without
         it and without ``dx`` they are never materialised (``WgradOp.run_pooled``)."""
-        eng, L, st = self.eng, hip.lib(), hip.stream_ptr(self.device)
+        eng, st = self.eng, hip.stream_ptr(self.device)
         # (``acts_override`` = (activation views, plane strides): the clips are a slice of a larger forward, loss_and_grads_grouped)
         acts, act_plane = acts_override if acts_override is not None else self._acts(nb)
         grad, layout = g_feat, 0
@@ -157,30 +152,26 @@ class TrainEngine:
             sc = inv = None
             if scaled:
                 scb = eng._buf("gscale%d" % li, (4,), torch.float32)
-                hip.check(L.vd_absmax_scale(hip.ptr(grad), ctypes.c_int64(grad.numel()), ctypes.c_float(GRAD_TARGET()),
-                                            hip.ptr(scb), st), "vd_absmax_scale")
+                hip.run("vd_absmax_scale", hip.ptr(grad), grad.numel(), GRAD_TARGET(), hip.ptr(scb), st)
                 sc, inv = scb, scb[1:]
             if dense:
                 dy = eng._buf("dy%d" % li, (eng.planes_bwd, nslots, 8), torch.int16)
                 lo = dy[1] if eng.planes_bwd == 2 else None
-                hip.check(L.vd_unpool_relu_bwd(hip.ptr(grad), hip.ptr(am[li]), ctypes.c_int64(nb), cout, To, Ho, Wo, pt, T, OH, OW,
-                                               layout, hip.ptr(dy[0]), hip.ptr(lo), eng.prec_bwd, hip.ptr(sc), st),
-                          "vd_unpool_relu_bwd")
+                hip.run("vd_unpool_relu_bwd", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To, Ho, Wo, pt, T, OH, OW, layout,
+                        hip.ptr(dy[0]), hip.ptr(lo), eng.prec_bwd, hip.ptr(sc), st)
             if g is not None:
                 if side is not None:
                     side.wait_stream(main)          # the level's gradient and its scale are queued on the main stream
                 with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
                     # bias gradient from the pooled gradient (the dense dy has one non-zero per live pool window)
                     if hip.deterministic():
-                        nsc = int(L.vd_bias_grad_pooled_scratch_floats(ctypes.c_int64(nb), cout, ctypes.c_int64(To * Ho * Wo)))
+                        nsc = int(hip.lib().vd_bias_grad_pooled_scratch_floats(nb, cout, To * Ho * Wo))
                         bsc = eng._buf("bias_part%d" % li, (nsc,), torch.float32)
-                        hip.check(L.vd_bias_grad_pooled_ordered(hip.ptr(grad), hip.ptr(am[li]), ctypes.c_int64(nb), cout,
-                                                                ctypes.c_int64(To * Ho * Wo), layout, hip.ptr(bsc), hip.ptr(g[2 * li + 1]),
-                                                                hip.stream_ptr(self.device)), "vd_bias_grad_pooled_ordered")
+                        hip.run("vd_bias_grad_pooled_ordered", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To * Ho * Wo, layout,
+                                hip.ptr(bsc), hip.ptr(g[2 * li + 1]), hip.stream_ptr(self.device))
                     else:
-                        hip.check(L.vd_bias_grad_pooled(hip.ptr(grad), hip.ptr(am[li]), ctypes.c_int64(nb), cout,
-                                                        ctypes.c_int64(To * Ho * Wo), layout, hip.ptr(g[2 * li + 1]),
-                                                        hip.stream_ptr(self.device)), "vd_bias_grad_pooled")
+                        hip.run("vd_bias_grad_pooled", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To * Ho * Wo, layout,
+                                hip.ptr(g[2 * li + 1]), hip.stream_ptr(self.device))
                     op = self._wgrad(li, nb)
                     # pooled gradient -> packed B operand of the weight-gradient program in one pass (4-8x fewer bytes than
                     # re-reading the dense slots, which for the first layer are not even written when nobody else needs them)
@@ -206,7 +197,7 @@ class TrainEngine:
         tensors in ``parameters()`` order, mask (B,C,Tp) dropout multipliers or None.
         Returns (mean CE loss [device scalar], logits (B,K), [8 gradient tensors]).  ``state`` (a dict)
         receives what a second-order pass needs (GradMatchEngine)."""
-        eng, L, st = self.eng, hip.lib(), hip.stream_ptr(self.device)
+        eng, st = self.eng, hip.stream_ptr(self.device)
         B = int(x.shape[0])
         x = x.detach().to(torch.float32).contiguous()
         labels = labels.to(self.device, torch.int64).contiguous()
@@ -220,7 +211,7 @@ class TrainEngine:
         logits = hs["logits"]
         loss_c = torch.empty(B, dtype=torch.float32, device=self.device)
         dlog = torch.empty((B, self.K), dtype=torch.float32, device=self.device)
-        hip.check(L.vd_ce_loss(hip.ptr(logits), hip.ptr(labels), B, self.K, hip.ptr(loss_c), hip.ptr(dlog), st), "vd_ce_loss")
+        hip.run("vd_ce_loss", hip.ptr(logits), hip.ptr(labels), B, self.K, hip.ptr(loss_c), hip.ptr(dlog), st)
         self.gflat.zero_()
         g = self.grads()
         g_feat = self.head_backward(hs, dlog, g[6], g[7])
@@ -238,7 +229,7 @@ class TrainEngine:
         leaves a quarter of the chip idle in the last level and a tail in the others -- and one backward per sub-batch on its slice
         of the kept activations / arg-max bytes.  Returns (losses (groups,), logits, [8 gradients] per sub-batch); equal to
         per-sub-batch calls (tests/test_gpu_train.py::test_grouped_real_batches_equal_separate_calls)."""
-        eng, L, st = self.eng, hip.lib(), hip.stream_ptr(self.device)
+        eng, st = self.eng, hip.stream_ptr(self.device)
         B = int(x.shape[0])
         if groups < 1 or B % groups != 0:
             raise ValueError("loss_and_grads_grouped: %d clips do not split into %d equal sub-batches" % (B, groups))
@@ -257,8 +248,8 @@ class TrainEngine:
         dlog = torch.empty((B, self.K), dtype=torch.float32, device=self.device)
         for k in range(groups):                 # (per sub-batch: vd_ce_loss scales the logit gradient by 1 / its batch size -- exactly what a
             sl = slice(k * per, (k + 1) * per)  #  separate call does; rescaling a 1 / B gradient would differ in the last bit, which the
-            hip.check(L.vd_ce_loss(hip.ptr(logits[sl]), hip.ptr(labels[sl]), per, self.K, hip.ptr(loss_c[sl]),   # f16 passes' power-of-two
-                                   hip.ptr(dlog[sl]), st), "vd_ce_loss")                                         #  scaling can amplify)
+            hip.run("vd_ce_loss", hip.ptr(logits[sl]), hip.ptr(labels[sl]), per, self.K, hip.ptr(loss_c[sl]),    # f16 passes' power-of-two
+                    hip.ptr(dlog[sl]), st)                                                                       #  scaling can amplify)
         acts, act_plane = self._acts(nb)
         per1, per2, nf = act_plane[1] // nb, act_plane[2] // nb, eng.num_feat
         outs = []
@@ -280,16 +271,15 @@ class TrainEngine:
                  lr: float, momentum: float, weight_decay: float) -> List[torch.Tensor]:
         """In-place torch.optim.SGD(momentum, weight_decay) update; returns the momentum buffers
         (created on first use, as torch does)."""
-        L, st = hip.lib(), hip.stream_ptr(self.device)
+        st = hip.stream_ptr(self.device)
         out = []
         for p, gr, b in zip(params, grads, bufs):
             first = b is None
             if first:
                 b = torch.empty_like(p, memory_format=torch.contiguous_format)
             assert p.is_contiguous() and p.dtype == torch.float32
-            hip.check(L.vd_sgd_momentum_wd(hip.ptr(p), hip.ptr(b), hip.ptr(gr), ctypes.c_int64(p.numel()), ctypes.c_float(lr),
-                                           ctypes.c_float(momentum), ctypes.c_float(weight_decay), int(first), st),
-                      "vd_sgd_momentum_wd")
+            hip.run("vd_sgd_momentum_wd", hip.ptr(p), hip.ptr(b), hip.ptr(gr), p.numel(), lr, momentum, weight_decay, int(first),
+                    st)
             out.append(b)
         return out
 
@@ -357,7 +347,7 @@ class GradMatchEngine(TrainEngine):
     def _forward(self, x, params):
         if self.scaled:      # the engine's own fp16 hi+lo forward: its kept activations and pixel rows ARE the sweeps' operands
             return TrainEngine._forward(self, x, params)
-        eng, ef, L, st = self.eng, self.eng_fwd, hip.lib(), hip.stream_ptr(self.device)
+        eng, ef, st = self.eng, self.eng_fwd, hip.stream_ptr(self.device)
         ef.set_weights(params[:6])
         keep_ws, ef._ws = ef._ws, {}
         try:
@@ -369,13 +359,13 @@ class GradMatchEngine(TrainEngine):
             for name, n in (("act1", nb * per1), ("act2", nb * per2)):
                 src = ef._buf(name, (2, n, 8), torch.int16)
                 dst = eng._buf(name, (eng.planes, n, 8), torch.int16)
-                hip.check(L.vd_resplit_slots(hip.ptr(src[0]), hip.ptr(src[1]), ctypes.c_int64(n * 8), ef.prec, hip.ptr(dst[0]),
-                                             hip.ptr(dst[1] if eng.planes == 2 else None), eng.prec, st), "vd_resplit_slots")
+                hip.run("vd_resplit_slots", hip.ptr(src[0]), hip.ptr(src[1]), n * 8, ef.prec, hip.ptr(dst[0]),
+                        hip.ptr(dst[1] if eng.planes == 2 else None), eng.prec, st)
             rowp = P.pix_row_pitch(g.width)
             n_slots0 = nb * g.frames * 3 * g.height * (rowp // 8)
             slots0 = eng._buf("slots0", (eng.planes, n_slots0, 8), torch.int16)
-            hip.check(L.vd_pix2rows(hip.ptr(x), hip.ptr(None), ctypes.c_int64(nb), g.frames, g.height, g.width, hip.ptr(slots0[0]),
-                                     hip.ptr(slots0[1] if eng.planes == 2 else None), eng.prec, st), "vd_pix2rows")
+            hip.run("vd_pix2rows", hip.ptr(x), hip.ptr(None), nb, g.frames, g.height, g.width, hip.ptr(slots0[0]),
+                    hip.ptr(slots0[1] if eng.planes == 2 else None), eng.prec, st)
         finally:
             ef._ws = keep_ws
         return feats, nb, (am0, am1, am2)
@@ -399,14 +389,13 @@ class GradMatchEngine(TrainEngine):
     def _absmax_scale(self, t: torch.Tensor, name: str, target: float) -> torch.Tensor:
         """[2^k, 2^-k, scratch, -] on the device with max|t| * 2^k in [target / 2, target) (vd_absmax_scale)."""
         scb = self._scale_buf(name)
-        hip.check(hip.lib().vd_absmax_scale(hip.ptr(t), ctypes.c_int64(t.numel()), ctypes.c_float(target), hip.ptr(scb),
-                                            hip.stream_ptr(self.device)), "vd_absmax_scale")
+        hip.run("vd_absmax_scale", hip.ptr(t), t.numel(), target, hip.ptr(scb), hip.stream_ptr(self.device))
         return scb
 
     def _combine(self, a: torch.Tensor, b: Optional[torch.Tensor], mode: int, name: str) -> torch.Tensor:
         """mode 0: [a0 * b0, 1 / (a0 * b0)]; mode 1: [min(a0, b0), 1 / min] (device scalars, vd_scale_combine)."""
         out = self._scale_buf(name)
-        hip.check(hip.lib().vd_scale_combine(hip.ptr(a), hip.ptr(b), mode, hip.ptr(out), hip.stream_ptr(self.device)), "vd_scale_combine")
+        hip.run("vd_scale_combine", hip.ptr(a), hip.ptr(b), mode, hip.ptr(out), hip.stream_ptr(self.device))
         return out
 
     def _pack_adjoint(self, W: Sequence[torch.Tensor], V: Sequence[torch.Tensor]) -> None:
@@ -460,7 +449,7 @@ class GradMatchEngine(TrainEngine):
             assert off % 4 == 0
             dp.params.src_split_off4 = off // 4
         if self.scaled:
-            L, st = hip.lib(), hip.stream_ptr(self.device)
+            st = hip.stream_ptr(self.device)
             g32 = [eng._buf("gbar32_1", (n1 * 8,), torch.float32), eng._buf("gbar32_2", (n2 * 8,), torch.float32)]
             self.sel[0].run(slots0, n_slots0, V[1], g32[0].data_ptr(), 0, am[0], nb, out_scale=self._sv[0][1:])
             self._sg = [None, None, None]
@@ -470,8 +459,8 @@ class GradMatchEngine(TrainEngine):
                 sg = self._absmax_scale(g32[li - 1], "gscale_up%d" % li, self.V_TARGET)
                 s_l = self._combine(sg, self._sv[li], 1, "sscale%d" % li)
                 self._sg[li] = s_l
-                hip.check(L.vd_split_scaled(hip.ptr(g32[li - 1]), ctypes.c_int64(g32[li - 1].numel()), hip.ptr(s_l), hip.ptr(gb[0]),
-                                            hip.ptr(gb[1]), eng.prec, st), "vd_split_scaled")
+                hip.run("vd_split_scaled", hip.ptr(g32[li - 1]), g32[li - 1].numel(), hip.ptr(s_l), hip.ptr(gb[0]), hip.ptr(gb[1]),
+                        eng.prec, st)
                 self.sel[li].pack(torch.cat([V[2 * li] * s_l[0], W[2 * li]], dim=1).contiguous())
                 dst = g32[1].data_ptr() if li == 1 else gbar3.data_ptr()
                 self.sel[li].run(a, n_a, V[2 * li + 1], dst, 0, am[li], nb, out_scale=s_l[1:])
@@ -484,7 +473,7 @@ class GradMatchEngine(TrainEngine):
     def _down_sweep(self, nb: int, am, abar: torch.Tensor, x: torch.Tensor, hv: Optional[Sequence[torch.Tensor]]) -> torch.Tensor:
         """abar_l = convT(P_l^T abar_{l+1}, W_l) + convT(dz_l, V_l) from abar_3 = ``abar`` down to the pixels; with ``hv`` the
         parameter side (weight / bias adjoints of the three conv levels) is accumulated into hv[0..5]."""
-        eng, geo, L, st = self.eng, self.geo, hip.lib(), hip.stream_ptr(self.device)
+        eng, geo, st = self.eng, self.geo, hip.stream_ptr(self.device)
         _, n1, n2, _, act1, act2, gbar1, gbar2 = self._sweep_bufs(nb)
         dx = torch.empty((nb, geo.frames, geo.channel, geo.height, geo.width), dtype=torch.float32, device=self.device)
         grad, layout = abar, 0
@@ -504,18 +493,16 @@ class GradMatchEngine(TrainEngine):
                 inv_dv = self._combine(gs, self._sv[li], 0, "dvscale%d" % li)[1:]
                 if hv and li > 0:
                     inv_gd = self._combine(gs, self._sg[li], 0, "gdscale%d" % li)[1:]
-            hip.check(L.vd_unpool_relu_bwd(hip.ptr(grad), hip.ptr(am[li]), ctypes.c_int64(nb), cout, To, Ho, Wo, pt, T, OH,
-                                           OW, layout, hip.ptr(zb[0]), hip.ptr(lo), eng.prec_bwd, hip.ptr(sz), st),
-                      "vd_unpool_relu_bwd")
+            hip.run("vd_unpool_relu_bwd", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To, Ho, Wo, pt, T, OH, OW, layout,
+                    hip.ptr(zb[0]), hip.ptr(lo), eng.prec_bwd, hip.ptr(sz), st)
             out = dx if li == 0 else eng._buf("ax%d" % li, (nb, t, h, w, cin), torch.float32)
             run_together(eng.bwd[li], zb, nslots, None, out.data_ptr(), 0, None, nb, out_scale=inv_z)
             run_together(self.bwdV[li], dy, nslots, None, out.data_ptr(), 0, None, nb, out_scale=inv_dv)   # (accumulates on top of the stores above)
             if hv:
                 # parameter side: z_l = conv(a_l, W_l) + b_l carries zbar_l, and g_{a_l} = convT(dz_l, W_l) carries gbar_l
                 op = self._wgrad(li, nb)
-                hip.check(L.vd_bias_grad_pooled(hip.ptr(grad), hip.ptr(am[li]), ctypes.c_int64(nb), cout,
-                                                ctypes.c_int64(To * Ho * Wo), layout, hip.ptr(hv[2 * li + 1]), st),
-                          "vd_bias_grad_pooled")
+                hip.run("vd_bias_grad_pooled", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To * Ho * Wo, layout,
+                        hip.ptr(hv[2 * li + 1]), st)
                 if li == 0:
                     op.run(x, True, 0, zb, nslots, hv[0], out_scale=inv_z)
                 else:
@@ -538,18 +525,17 @@ class GradMatchEngine(TrainEngine):
         """Second-order pass through the head.  ``hessian``: fused with the Hessian of the mean cross-entropy (dlog must
         then be that loss's own logit gradient) -- the trainers' path; otherwise the adjoint of ``dlog`` is returned
         for the caller's loss to chain through.  -> (abar_feats, wbar, bbar, dlogbar)."""
-        L, st = hip.lib(), hip.stream_ptr(self.device)
+        st = hip.stream_ptr(self.device)
         nb = int(dlog.shape[0])
         kt, kh, kw = self.pool_kernel
         abar = torch.empty((nb, self.eng.num_feat), dtype=torch.float32, device=self.device)
         wbar = torch.zeros((self.K, self.C), dtype=torch.float32, device=self.device) if want_params else None
         bbar = torch.zeros(self.K, dtype=torch.float32, device=self.device) if want_params else None
         dlogbar = None if hessian else torch.empty((nb, self.K), dtype=torch.float32, device=self.device)
-        hip.check(L.vd_head_second_order(hip.ptr(hs["logits"] if hessian else None), hip.ptr(dlog), hip.ptr(hs["amt"]),
-                                         hip.ptr(hs["dropped"]), hip.ptr(hs["mask"]), hip.ptr(hs["wl"]), hip.ptr(v_w),
-                                         hip.ptr(v_b), hip.ptr(gbar_feat), ctypes.c_int64(nb), self.C, self.To, self.Ho, self.Wo,
-                                         kt, kh, kw, self.K, hip.ptr(abar), hip.ptr(wbar), hip.ptr(bbar), hip.ptr(dlogbar), st),
-                  "vd_head_second_order")
+        hip.run("vd_head_second_order", hip.ptr(hs["logits"] if hessian else None), hip.ptr(dlog), hip.ptr(hs["amt"]),
+                hip.ptr(hs["dropped"]), hip.ptr(hs["mask"]), hip.ptr(hs["wl"]), hip.ptr(v_w), hip.ptr(v_b), hip.ptr(gbar_feat), nb,
+                self.C, self.To, self.Ho, self.Wo, kt, kh, kw, self.K, hip.ptr(abar), hip.ptr(wbar), hip.ptr(bbar),
+                hip.ptr(dlogbar), st)
         return abar, wbar, bbar, dlogbar
 
     def vjp(self, state: dict, v: Sequence[Optional[torch.Tensor]], params: Sequence[torch.Tensor],

@@ -152,9 +152,8 @@ class _HallucinatorFunction(torch.autograd.Function):
         w = weight.detach().float().contiguous()
         b = bias.detach().float().contiguous()
         out = torch.empty((n, T, 3, H, W), dtype=torch.float32, device=dynamic.device)
-        hip.check(hip.lib().vd_hallucinator_fwd(hip.ptr(st), hip.ptr(dy), None, None, hip.ptr(w), hip.ptr(b),
-                                                n, T, H, W, hip.ptr(out), hip.stream_ptr(out.device)),
-                  "vd_hallucinator_fwd")
+        hip.run("vd_hallucinator_fwd", hip.ptr(st), hip.ptr(dy), None, None, hip.ptr(w), hip.ptr(b), n, T, H, W, hip.ptr(out),
+                hip.stream_ptr(out.device))
         ctx.save_for_backward(st, dy, w)
         return out
 
@@ -168,9 +167,8 @@ class _HallucinatorFunction(torch.autograd.Function):
         g_stat = torch.zeros_like(st) if need_static else None
         g_w = torch.zeros(324, dtype=torch.float32, device=g.device)
         g_b = torch.zeros(3, dtype=torch.float32, device=g.device)
-        hip.check(hip.lib().vd_hallucinator_bwd(hip.ptr(g), hip.ptr(st), hip.ptr(dy), None, None, hip.ptr(w),
-                                                n, T, H, W, hip.ptr(g_dyn), hip.ptr(g_stat), hip.ptr(g_w),
-                                                hip.ptr(g_b), hip.stream_ptr(g.device)), "vd_hallucinator_bwd")
+        hip.run("vd_hallucinator_bwd", hip.ptr(g), hip.ptr(st), hip.ptr(dy), None, None, hip.ptr(w), n, T, H, W, hip.ptr(g_dyn),
+                hip.ptr(g_stat), hip.ptr(g_w), hip.ptr(g_b), hip.stream_ptr(g.device))
         return g_stat, g_dyn, g_w.view(3, 4, 3, 3, 3), g_b
 
 
@@ -315,7 +313,7 @@ class _MatchLossFunction(torch.autograd.Function):
     def forward(ctx, mode, n, *tensors):
         gw_syn, gw_real = tensors[:n], tensors[n:]
         dev = gw_syn[0].device
-        L, st = hip.lib(), hip.stream_ptr(dev)
+        st = hip.stream_ptr(dev)
         acc = torch.zeros(5, dtype=torch.float32, device=dev)
         keep, batches = [], [hip.VdMatchBatch()]
         for gs, gr in zip(gw_syn, gw_real):
@@ -327,7 +325,7 @@ class _MatchLossFunction(torch.autograd.Function):
             if rows <= 0 or ln <= 0:
                 keep.append(None)
                 continue
-            if batches[-1].nseg == 16:
+            if batches[-1].nseg == hip.VD_MATCH_MAX_SEG:
                 batches.append(hip.VdMatchBatch())
             b = batches[-1]
             b.reserved = (1, 2, 28)[mode]               # the sums this metric reads: acc[0] / acc[1] / acc[2..4]
@@ -336,7 +334,7 @@ class _MatchLossFunction(torch.autograd.Function):
             b.nseg += 1
             keep.append((gs_c, gr_c, rows, ln))
         for b in batches:
-            hip.check(L.vd_match_rows_fwd_multi(ctypes.byref(b), hip.ptr(acc), st), "vd_match_rows_fwd_multi")
+            hip.run("vd_match_rows_fwd_multi", ctypes.byref(b), hip.ptr(acc), st)
         ctx.keep, ctx.mode, ctx.n = keep, mode, n
         ctx.acc = acc
         if mode == 0:
@@ -347,7 +345,6 @@ class _MatchLossFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        L = hip.lib()
         gout = gout.detach().float().contiguous().view(1)
         st = hip.stream_ptr(gout.device)
         grads, batches = [], [hip.VdMatchBatch()]
@@ -357,7 +354,7 @@ class _MatchLossFunction(torch.autograd.Function):
                 continue
             gs_c, gr_c, rows, ln = item
             g = torch.empty_like(gs_c)
-            if batches[-1].nseg == 16:
+            if batches[-1].nseg == hip.VD_MATCH_MAX_SEG:
                 batches.append(hip.VdMatchBatch())
             b = batches[-1]
             sg = b.seg[b.nseg]
@@ -365,8 +362,7 @@ class _MatchLossFunction(torch.autograd.Function):
             b.nseg += 1
             grads.append(g)
         for b in batches:
-            hip.check(L.vd_match_rows_bwd_multi(ctypes.byref(b), ctx.mode, hip.ptr(ctx.acc), hip.ptr(gout), st),
-                      "vd_match_rows_bwd_multi")
+            hip.run("vd_match_rows_bwd_multi", ctypes.byref(b), ctx.mode, hip.ptr(ctx.acc), hip.ptr(gout), st)
         return (None, None) + tuple(grads) + (None,) * ctx.n
 
 
