@@ -1244,17 +1244,71 @@ def unflatten_params(flat: torch.Tensor, num_classes: int) -> List[torch.Tensor]
     return out
 
 
+class FlatChain:
+    """The flat-parameter chain of an MTT iteration on the ``vdt_`` kernels (include/vd_traj.h, csrc/traj.hip): owns the
+    reduction scratch, the 4-double loss record, the fp64 d/d syn_lr accumulator and the two vectors that live through the
+    reverse sweep (thetabar, v), all sized on first use.  Vectors are contiguous fp32 tensors of one length on ``device``,
+    16-byte aligned (fresh torch allocations and ``ExpertStore`` rows are)."""
+
+    def __init__(self, device):
+        from . import hip
+        self.hip, self.device = hip, torch.device(device)
+        self.n = 0
+
+    def _size(self, n: int) -> None:
+        if n != self.n:
+            need = int(self.hip.lib().vdt_traj_scratch_doubles(n))
+            self.scratch = torch.empty((need,), dtype=torch.float64, device=self.device)
+            self.out = torch.zeros((4,), dtype=torch.float64, device=self.device)
+            self.g_lr = torch.zeros((1,), dtype=torch.float64, device=self.device)
+            self.tbar = torch.empty((n,), dtype=torch.float32, device=self.device)
+            self.v = torch.empty((n,), dtype=torch.float32, device=self.device)
+            self.n = n
+
+    def _check(self, *vectors) -> int:
+        n = int(vectors[0].numel())
+        for t in vectors:
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and int(t.numel()) == n):
+                raise RuntimeError("FlatChain: contiguous fp32 device vectors of one length (there is no CPU path)")
+        return n
+
+    def step(self, theta: torch.Tensor, g: torch.Tensor, lr: torch.Tensor) -> torch.Tensor:
+        """-> a fresh theta - lr * g (``lr``: 0-dim fp32 device tensor)."""
+        n = self._check(theta, g)
+        out = torch.empty((n,), dtype=torch.float32, device=self.device)
+        self.hip.run("vdt_traj_step", theta.data_ptr(), g.data_ptr(), lr.data_ptr(), n, out.data_ptr(), self.hip.stream_ptr(self.device))
+        return out
+
+    def loss(self, theta: torch.Tensor, theta0: torch.Tensor, target: torch.Tensor):
+        """-> (record [dist, dist0, dist / dist0, 0] of 4 device doubles, thetabar_N); both owned by this object."""
+        n = self._check(theta, theta0, target)
+        self._size(n)
+        self.hip.run("vdt_traj_loss", theta.data_ptr(), theta0.data_ptr(), target.data_ptr(), n, self.scratch.data_ptr(),
+                     self.out.data_ptr(), self.tbar.data_ptr(), self.hip.stream_ptr(self.device))
+        self.g_lr.zero_()
+        return self.out, self.tbar
+
+    def adjoint(self, hv: Optional[torch.Tensor], g: torch.Tensor, lr: torch.Tensor, share: float) -> torch.Tensor:
+        """One reverse step on the thetabar of ``loss``: thetabar += hv (None: the first), g_lr -= <thetabar, g>,
+        -> v = -(lr * share) * thetabar (this object's buffer: consumed before the next call)."""
+        n = self._check(self.tbar, hv, g)
+        self.hip.run("vdt_traj_adjoint", self.tbar.data_ptr(), self.hip.ptr(hv), g.data_ptr(), lr.data_ptr(), float(share), n,
+                     self.scratch.data_ptr(), self.g_lr.data_ptr(), self.v.data_ptr(), self.hip.stream_ptr(self.device))
+        return self.v
+
+
 class HipMTTOps:
     """Device operations of the unrolled student loop on the HIP path (train.GradMatchEngine)."""
 
     def __init__(self, geo: P.NetGeometry, num_classes: int, device, dropout_p: float = 0.5,
-                 batch_hint: Optional[int] = None):
+                 batch_hint: Optional[int] = None, fused_flat: bool = False):
         from . import hip, networks, train
         self.hip, self.device = hip, torch.device(device)
         pool = (2, 2, 2) if geo.height > 64 else (2, 1, 1)          # networks.py:733
         self.te = train.GradMatchEngine(geo, num_classes, pool, device, prec=networks.get_precision()["match"],
                                         batch_hint=batch_hint)
         self.dropout_p = float(dropout_p)
+        self.flat = FlatChain(self.device) if fused_flat else None      # MTTTrainer.step: the vdt_ kernels instead of torch expressions
 
     def grads(self, params, x, labels):
         """-> ([8 gradients of the mean CE], handle for hvp)."""
@@ -1297,8 +1351,10 @@ class MTTTrainer:
 
     def __init__(self, ops, num_classes: int, image_syn: torch.Tensor, label_syn: torch.Tensor, syn_lr: float,
                  lr_img: float, lr_lr: float, syn_steps: int, batch_syn: int, expert_epochs: int, max_start_epoch: int,
-                 momentum: float = 0.5, rank: int = 0, world: int = 1):
+                 momentum: float = 0.5, rank: int = 0, world: int = 1, train_lr: bool = True):
         self.ops, self.num_classes = ops, num_classes
+        self.train_lr = bool(train_lr)      # False (the reference's default, --train_lr is a flag): syn_lr and its momentum are not stepped
+        self.last_start_epoch = None
         self.image_syn, self.label_syn = image_syn.contiguous(), label_syn
         self.buf = torch.zeros_like(self.image_syn)
         dev = self.image_syn.device
@@ -1345,14 +1401,24 @@ class MTTTrainer:
         return flat
 
     def step(self, it: int, trajectory, start_epoch: Optional[int] = None, index_chunks=None, update: bool = True):
-        """``trajectory``: one expert (list over epochs of the 8 parameter tensors, as stored in
-        ``replay_buffer_N.pt``, buffer.py:75-104).  Returns the grand loss as a 0-dim device tensor."""
+        """``trajectory``: one expert, either the list over epochs of the 8 parameter tensors as stored in
+        ``replay_buffer_N.pt`` (buffer.py:75-104) or an ``experts.FlatTrajectory``, whose rows are used as they lie on the device
+        (no copy, no ``cat``).  Returns the grand loss as a 0-dim device tensor.  With ``ops.flat`` set (``HipMTTOps(...,
+        fused_flat=True)``) the flat-parameter arithmetic runs on the ``vdt_`` kernels: the same float32 elementwise values, the
+        two distances and d/d syn_lr summed in fp64 in a fixed order."""
+        from .experts import FlatTrajectory
         dev = self.image_syn.device
         rng = np.random.default_rng([it, 17])
         if start_epoch is None:
             start_epoch = int(rng.integers(0, self.max_start_epoch))
-        start = [p.to(dev, torch.float32) for p in trajectory[start_epoch]]
-        target = flatten_params([p.to(dev, torch.float32) for p in trajectory[start_epoch + self.expert_epochs]])
+        self.last_start_epoch = int(start_epoch)
+        if isinstance(trajectory, FlatTrajectory):
+            theta0 = trajectory.row(start_epoch)
+            target = trajectory.row(start_epoch + self.expert_epochs)
+        else:
+            start = [p.to(dev, torch.float32) for p in trajectory[start_epoch]]
+            target = flatten_params([p.to(dev, torch.float32) for p in trajectory[start_epoch + self.expert_epochs]])
+            theta0 = flatten_params(start)
         if index_chunks is None:            # torch.randperm + split + pop() of distill_baseline.py:226-233, seeded per iteration
             index_chunks, pending = [], []
             for _ in range(self.syn_steps):
@@ -1361,8 +1427,8 @@ class MTTTrainer:
                     pending = list(torch.split(perm, self.batch_syn))
                 index_chunks.append(pending.pop())
         self._begin(dev)
-        theta0 = flatten_params(start)
-        theta = theta0.clone()
+        flat = getattr(self.ops, "flat", None)
+        theta = theta0 if flat is not None else theta0.clone()          # (the fused step is out of place: theta0 stays as it is)
         tape = []
         for step, idx in enumerate(index_chunks):
             idx = idx.to(dev)
@@ -1380,28 +1446,45 @@ class MTTTrainer:
                 g, handle, ctx = torch.zeros_like(theta), None, None
             g = self._allreduce(g)
             tape.append((ctx, share, handle, g))
-            theta = theta - self.syn_lr * g
-        dist0 = ((theta0 - target) ** 2).sum()
-        grand = ((theta - target) ** 2).sum() / dist0
-        # ---- reverse sweep ---------------------------------------------------------------------
-        tbar = 2.0 * (theta - target) / dist0
-        g_lr = torch.zeros((), dtype=torch.float32, device=dev)
-        for ctx, share, handle, g in reversed(tape):
-            g_lr = g_lr - (tbar * g).sum()
-            if handle is not None:
-                v = unflatten_params(tbar * (-self.syn_lr * share), self.num_classes)
-                dx, hv = self.ops.hvp(handle, v)
-                self._push(ctx, dx)
-                hv = flatten_params(hv)
-            else:
-                hv = torch.zeros_like(tbar)
-            tbar = tbar + self._allreduce(hv)
+            theta = flat.step(theta, g, self.syn_lr) if flat is not None else theta - self.syn_lr * g
+        if flat is not None:
+            # ---- loss and reverse sweep on the vdt_ kernels (include/vd_traj.h) -----------------------
+            record, _ = flat.loss(theta, theta0, target)
+            grand = record[2].to(torch.float32)
+            hv = None
+            for ctx, share, handle, g in reversed(tape):
+                v = flat.adjoint(hv, g, self.syn_lr, share)          # thetabar += hv of the step before; g_lr -= <thetabar, g>
+                if handle is not None:
+                    dx, hv = self.ops.hvp(handle, unflatten_params(v, self.num_classes))
+                    self._push(ctx, dx)
+                    hv = flatten_params(hv)
+                else:
+                    hv = torch.zeros_like(g)
+                hv = self._allreduce(hv)
+            g_lr = flat.g_lr[0].to(torch.float32)
+        else:
+            dist0 = ((theta0 - target) ** 2).sum()
+            grand = ((theta - target) ** 2).sum() / dist0
+            # ---- reverse sweep ---------------------------------------------------------------------
+            tbar = 2.0 * (theta - target) / dist0
+            g_lr = torch.zeros((), dtype=torch.float32, device=dev)
+            for ctx, share, handle, g in reversed(tape):
+                g_lr = g_lr - (tbar * g).sum()
+                if handle is not None:
+                    v = unflatten_params(tbar * (-self.syn_lr * share), self.num_classes)
+                    dx, hv = self.ops.hvp(handle, v)
+                    self._push(ctx, dx)
+                    hv = flatten_params(hv)
+                else:
+                    hv = torch.zeros_like(tbar)
+                tbar = tbar + self._allreduce(hv)
         self.last_grads = self._finish(update) + (g_lr,)
         self.last_tape = tape if self.keep_tape else None
         if update:
-            mu = self.LR_MOMENTUM
-            self.lr_buf = g_lr.clone() if self.steps_done == 0 else mu * self.lr_buf + g_lr
-            self.syn_lr = torch.clamp(self.syn_lr - self.lr_lr * self.lr_buf, min=0.001)         # .clip(min=0.001), :269
+            if self.train_lr:
+                mu = self.LR_MOMENTUM
+                self.lr_buf = g_lr.clone() if self.steps_done == 0 else mu * self.lr_buf + g_lr
+                self.syn_lr = torch.clamp(self.syn_lr - self.lr_lr * self.lr_buf, min=0.001)         # .clip(min=0.001), :269
             self.steps_done += 1
         return grand
 
@@ -1420,12 +1503,12 @@ class S2DMTTTrainer(MTTTrainer):
     def __init__(self, ops, num_classes: int, vpc: int, spc: int, dpc: int, static_syn: torch.Tensor, dynamic_syn: torch.Tensor,
                  hal_w: torch.Tensor, hal_b: torch.Tensor, syn_lr: float, lr_dynamic: float, lr_hal: float, lr_lr: float,
                  syn_steps: int, batch_syn: int, expert_epochs: int, max_start_epoch: int, lr_static: float = 0.0,
-                 train_static: bool = False, momentum: float = 0.95, rank: int = 0, world: int = 1):
+                 train_static: bool = False, momentum: float = 0.95, rank: int = 0, world: int = 1, train_lr: bool = True):
         self.vpc, self.spc, self.dpc = int(vpc), int(spc), int(dpc)
         self.static = static_syn.contiguous()
         self.dynamic = dynamic_syn.reshape((-1,) + tuple(dynamic_syn.shape[2:])).contiguous()      # rows (class, dpc) flattened
         super().__init__(ops, num_classes, self.dynamic, None, syn_lr, lr_dynamic, lr_lr, syn_steps, batch_syn, expert_epochs,
-                         max_start_epoch, momentum=momentum, rank=rank, world=world)
+                         max_start_epoch, momentum=momentum, rank=rank, world=world, train_lr=train_lr)
         self.image_syn = self.dynamic                  # device / bookkeeping handle of the base class
         self.hal_w, self.hal_b = hal_w.clone().contiguous(), hal_b.clone().contiguous()
         self.lr_dynamic, self.lr_hal, self.lr_static = float(lr_dynamic), float(lr_hal), float(lr_static)

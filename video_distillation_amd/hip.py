@@ -19,10 +19,11 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvd_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernels.hip", "program.hip", "planner.cpp", "comm.cpp",
-                                                         "coreset.hip", "clips_sample.hip", "eval_stats.hip")]
+                                                         "coreset.hip", "clips_sample.hip", "eval_stats.hip", "traj.hip")]
 CSRC_HEADERS = [os.path.join(_HERE, "csrc", "frame_norm.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
 HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
+HEADER_TRAJ = os.path.join(_HERE, "..", "include", "vd_traj.h")      # the second public header: the vdt_ entry points (csrc/traj.hip)
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
@@ -120,7 +121,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER, *CSRC_HEADERS)
+        key = _file_hash(src, HEADER, HEADER_TRAJ, *CSRC_HEADERS)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -165,12 +166,12 @@ def library_stamp(path: str = None) -> Optional[str]:
 
 
 def sources_hash() -> str:
-    """sha256 (first 16 hex digits) over the kernel sources and the ABI header: what measurement files that are carried from one
+    """sha256 (first 16 hex digits) over the kernel sources and the two ABI headers: what measurement files that are carried from one
     run to the next (profiles/rNN_pmc_traffic.json -> bench.py's ``roofline.traffic``) are stamped with, so that a figure
     measured on other kernels is refused instead of quoted."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER] + CSRC_HEADERS:
+    for path in sorted(SOURCES) + [HEADER, HEADER_TRAJ] + CSRC_HEADERS:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -178,13 +179,14 @@ def sources_hash() -> str:
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
 _RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None, "const char*": ctypes.c_char_p}
-_PROTOTYPE = re.compile(r"(int64_t|int|void|const char\s*\*)\s*(vd_[a-z0-9_]+)\s*\(([^()]*)\)")
+_PROTOTYPE = re.compile(r"(int64_t|int|void|const char\s*\*)\s*(vdt?_[a-z0-9_]+)\s*\(([^()]*)\)")
 _PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+")
 
 
-def parse_header(text: str) -> dict:
-    """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses -> {name: (restype, [argtypes])}.  Anything
-    else -- a type outside the set, a statement that is not wholly a prototype -- is a ``ValueError`` that quotes it; no guesses."""
+def parse_header(text: str, where: str = "include/vd_hip.h") -> dict:
+    """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses (names ``vd_*``, or ``vdt_*`` for
+    include/vd_traj.h) -> {name: (restype, [argtypes])}.  Anything else -- a type outside the set, a statement that is not wholly
+    a prototype -- is a ``ValueError`` that quotes it; no guesses."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"typedef\s+struct\s*\w*\s*(\{[^{}]*\}\s*)?\w+\s*;", " ", text)
     text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|^[ \t]*\}[ \t]*$', " ", text, flags=re.M)      # (no directive is continued)
@@ -192,13 +194,13 @@ def parse_header(text: str) -> dict:
     for stmt in filter(None, (" ".join(part.split()) for part in text.split(";"))):
         m = _PROTOTYPE.fullmatch(stmt)
         if m is None or m.group(2) in sigs:
-            raise ValueError("include/vd_hip.h: not a prototype the binding understands, or a second one of its name: %r" % stmt)
+            raise ValueError("%s: not a prototype the binding understands, or a second one of its name: %r" % (where, stmt))
         ret, name, params = m.group(1).replace(" *", "*"), m.group(2), m.group(3).strip()
         argtypes = []
         for par in ([] if params == "void" else params.split(",")):
             pm = _PARAMETER.fullmatch(par.strip())
             if pm is None or not (pm.group(2) or pm.group(1) in _SCALARS):
-                raise ValueError("include/vd_hip.h: parameter %r of %r has no ctypes mapping" % (par.strip(), stmt))
+                raise ValueError("%s: parameter %r of %r has no ctypes mapping" % (where, par.strip(), stmt))
             argtypes.append(ctypes.c_void_p if pm.group(2) else _SCALARS[pm.group(1)])
         sigs[name] = (_RETURNS[ret], argtypes)
     return sigs
@@ -209,6 +211,18 @@ def signatures() -> dict:
     """{name: (restype, [argtypes])} of include/vd_hip.h, read and parsed once, when first asked for (binding a library does)."""
     with open(HEADER) as f:
         return parse_header(f.read())
+
+
+@functools.lru_cache(maxsize=None)
+def signatures_ext() -> dict:
+    """{name: (restype, [argtypes])} of include/vd_traj.h, the ``vdt_`` entry points of the same library (``signatures()`` and
+    ``EXPORTS`` are include/vd_hip.h alone)."""
+    with open(HEADER_TRAJ) as f:
+        sigs = parse_header(f.read(), "include/vd_traj.h")
+    other = [name for name in sigs if not name.startswith("vdt_")]
+    if other:
+        raise ValueError("include/vd_traj.h declares %s: its entry points carry the prefix vdt_" % ", ".join(other))
+    return sigs
 
 
 def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
@@ -225,9 +239,10 @@ class _Library(ctypes.CDLL):
 
 
 def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
-    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h."""
+    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h and
+    include/vd_traj.h."""
     L = _Library(path)
-    for name, (restype, argtypes) in signatures().items():
+    for name, (restype, argtypes) in list(signatures().items()) + list(signatures_ext().items()):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

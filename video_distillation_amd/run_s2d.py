@@ -17,7 +17,7 @@ Files under ``save_path/S2D_multis_DM/{dataset}_ipc{vpc}_{lr_dynamic}_{lr_hal}``
 ``hal_{it}.pt``, with a new best accuracy ``dynamic_best.pt`` / ``weights_best.pt``, and ``images_{it}.pt`` /
 ``images_best.pt`` (the static memory) only when it is trained.  Logging: JSON lines with the reference's wandb keys.
 
-Not here: the MTT branch (``S2DMTTTrainer`` is the library piece), the ``syn_{it}.png`` grid, wandb.  ``--train_lr`` /
+Not here: the MTT branch (its driver is ``video_distillation_amd.run_mtt --memories s2d``), the ``syn_{it}.png`` grid, wandb.  ``--train_lr`` /
 ``--lr_lr`` are left out: the DM branch steps ``optimizer_lr`` on a tensor no DM loss depends on.
 """
 from __future__ import annotations
