@@ -5,7 +5,7 @@
     python -m video_distillation_amd.run_coreset --dataset miniUCF101 --data_path D --method k-center --ipc 1 \\
         --pretrained_path net.pt
 
-Data as in run_dm (``run_dm.load_data``): ``--dataset synthetic`` (``--num_classes``, ``--pool_per_class``, ``--im_size``),
+Data as in run_dm (``run_dm.load_data``; the data flags, process setup and log are ``driver.py``'s): ``--dataset synthetic`` (``--num_classes``, ``--pool_per_class``, ``--im_size``),
 a frame-folder dataset under ``--data_path`` (decoded once, resident in HBM -- ``--preload`` is accepted and always in
 effect), or ``--data_file f.pt``.  Selection: ``coreset.build_synset`` (fp32-grade features, fp64 Gram, picks on the device);
 ``--kcenter reference`` reproduces the reference script's k-center output (ipc <= 2 only, see coreset.py).  Then
@@ -17,11 +17,12 @@ training epochs, where that test frequency would never test, the net is tested a
 from __future__ import annotations
 
 import argparse
-import json
 import os
 
 import numpy as np
 import torch
+
+from . import driver
 
 
 def build_parser():
@@ -42,13 +43,9 @@ def build_parser():
     p.add_argument('--save_path', type=str, default='.', help='path to save')
     p.add_argument('--frames', type=int, default=16, help='')
     p.add_argument('--preload', action='store_true', help='preload dataset (the pool is always resident)')
-    # run_dm's data options
-    p.add_argument('--data_file', type=str, default=None)
-    p.add_argument('--im_size', type=int, default=112)
-    p.add_argument('--num_classes', type=int, default=50, help='synthetic data only')
+    # the project's data options (run_dm.load_data reads them)
+    driver.add_data_flags(p)
     p.add_argument('--pool_per_class', type=int, default=93, help='synthetic data only')
-    p.add_argument('--test_videos', type=str, default='host', choices=['host', 'resident'],
-                   help='resident: whole test videos in HBM, clips drawn per read on the device (run_dm.load_data)')
     # this driver's own
     p.add_argument('--kcenter', type=str, default='greedy', choices=['greedy', 'reference'])
     p.add_argument('--log_file', type=str, default=None)
@@ -78,22 +75,12 @@ def run(args, log=None):
                          "(launch it without torch.distributed.run)")
     if args.method not in coreset.METHODS:
         raise NotImplementedError("--method %s (the reference knows herding and k-center)" % args.method)
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-    torch.cuda.set_device(device)
+    _, _, device = driver.start(use_cuda=True)
     geo = plan.NetGeometry(args.frames, args.im_size, args.im_size)
     pool, num_classes, _, testloader = load_data(args, 0, 1, geo, device)
     im_size = (int(pool.clips.shape[3]), int(pool.clips.shape[4]))
-    out = open(args.log_file, "a") if args.log_file else None
-
-    def emit(rec):
-        line = json.dumps(rec)
-        if log is not None:
-            log.append(rec)
-        print(line, flush=True)
-        if out:
-            out.write(line + "\n")
-            out.flush()
-
+    log = driver.JsonLog(args.log_file, 0, log)
+    emit = log.emit
     net = utils.get_network(args.model, 3, num_classes, im_size, frames=args.frames, dist=False).to(device)
     net.train()
     for param in list(net.parameters()):
@@ -126,8 +113,7 @@ def run(args, log=None):
                 accs.append(float(acc_test))
                 emit({"model": model_eval, "it_eval": it_eval, "acc_train": float(acc_train), "acc_test": float(acc_test)})
             emit({"model": model_eval, "acc_test_mean": float(np.mean(accs)), "acc_test_std": float(np.std(accs))})
-    if out:
-        out.close()
+    log.close()
     return image_syn, label_syn, index
 
 

@@ -9,24 +9,24 @@ Data: ``--dataset synthetic`` (randn clips); ``--dataset miniUCF101
 (the reference's frame folders, decoded once and kept in HBM: dataset.py; ``--test_videos resident`` keeps the test split's
 whole videos there too, so that evaluation draws its clips per read without decoding JPEGs); or ``--data_file f.pt`` holding
 {"clips": (N,T,3,H,W), "labels": (N,), "test_clips", "test_labels"}.  Logging: JSON lines with the reference's wandb keys
-(``Loss``, ``Accuracy/<model>``, ``Max_Accuracy/<model>``, ``Std/<model>``, ``Max_Std/<model>``).
+(``Loss``, ``Accuracy/<model>``, ``Max_Accuracy/<model>``, ``Std/<model>``, ``Max_Std/<model>``).  Process setup, log, the
+evaluation round and the project's own flags are shared with the other drivers (``driver.py``).
 """
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import sys
 import time
 
 import numpy as np
 import torch
 
+from . import driver
+
 
 def build_parser():
     p = argparse.ArgumentParser(description="DM distillation on MI355X")
     p.add_argument('--dataset', type=str, default='synthetic')
-    p.add_argument('--data_file', type=str, default=None)
     p.add_argument('--data_path', type=str, default='distill_utils/data')
     p.add_argument('--num_workers', type=int, default=8, help='decode threads of the preload')
     p.add_argument('--method', type=str, default='DM', choices=['DM'])
@@ -44,22 +44,11 @@ def build_parser():
     p.add_argument('--init', type=str, default='real', choices=['noise', 'real'])
     p.add_argument('--save_path', type=str, default='./logged_files')
     p.add_argument('--frames', type=int, default=16)
-    p.add_argument('--im_size', type=int, default=112)
-    p.add_argument('--num_classes', type=int, default=50, help='synthetic data only')
     p.add_argument('--pool_per_class', type=int, default=93, help='synthetic data only')
     p.add_argument('--prec_real', type=str, default='f16')
     p.add_argument('--prec_syn', type=str, default='f16x3')
-    p.add_argument('--log_file', type=str, default=None)
-    p.add_argument('--no_eval', action='store_true')
-    p.add_argument('--test_videos', type=str, default='host', choices=['host', 'resident'],
-                   help="host: the test loader decodes JPEGs per read; resident: whole test videos in HBM, clips drawn per read "
-                        "on the device (dataset.ResidentVideos; 'window' datasets only)")
-    p.add_argument('--eval_ranks', type=str, default='rank0', choices=['rank0', 'all'],
-                   help="rank0: rank 0 trains and tests the num_eval networks one after the other; all: the networks and their "
-                        "three test passes are dealt over all ranks (evalpool.evaluate_pool)")
-    p.add_argument('--eval_seed', type=int, default=None,
-                   help="--eval_ranks all: seed of the evaluation networks (default: a clock value drawn on rank 0); the "
-                        "evaluation at iteration `it` uses eval_seed + it")
+    driver.add_data_flags(p)
+    driver.add_eval_flags(p)
     return p
 
 
@@ -70,9 +59,7 @@ def load_data(args, rank, world, geo, device):
         from . import dataset as D
         _, im_size, num_classes, _, _, _, dst_train, dst_test, testloader = D.get_dataset(args.dataset, args.data_path,
                                                                                           img_size=(args.im_size, args.im_size))
-        # (rank 0 evaluates; with --eval_ranks all every rank does)
-        if getattr(args, 'test_videos', 'host') == 'resident' and (rank == 0 or getattr(args, 'eval_ranks', 'rank0') == 'all'):
-            testloader = D.resident_loader(dst_test, device, batch_size=testloader.batch_size, workers=args.num_workers)
+        testloader = driver.folder_test_loader(args, rank, device, dst_test, testloader)
         c_lo, c_hi = distill.class_range(num_classes, rank, world)
         pool = distill.RealPool.from_dataset(dst_train, num_classes, list(range(c_lo, c_hi)), device, workers=args.num_workers)
         return pool, num_classes, (c_lo, c_hi), testloader
@@ -91,25 +78,12 @@ def load_data(args, rank, world, geo, device):
     a, b = int(starts[c_lo]), int(starts[c_hi])
     offsets = [int(s) - a for s in starts[:-1]]
     pool = distill.RealPool(clips[a:b].to(device), counts, offsets)
-    test = None
-    if "test_clips" in blob:
-        test = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(blob["test_clips"].float(), blob["test_labels"].long()),
-                                           batch_size=64, shuffle=False)
-    return pool, num_classes, (c_lo, c_hi), test
+    return pool, num_classes, (c_lo, c_hi), driver.file_test_loader(blob)
 
 
 def run(args, backend=None, log=None):
     from . import checkpoint, distill, plan, utils
-    rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    use_cuda = backend is None
-    device = torch.device("cuda", local_rank) if use_cuda else torch.device("cpu")
-    if use_cuda:
-        torch.cuda.set_device(device)
-    if world > 1:
-        import torch.distributed as dist
-        if not dist.is_initialized():
-            dist.init_process_group(backend="nccl" if use_cuda else "gloo")
+    rank, world, device = driver.start(use_cuda=backend is None)
     geo = plan.NetGeometry(args.frames, args.im_size, args.im_size)
     pool, num_classes, (c_lo, c_hi), testloader = load_data(args, rank, world, geo, device)
     if backend is None:
@@ -123,27 +97,12 @@ def run(args, backend=None, log=None):
     eval_pool = utils.get_eval_pool(args.eval_mode, args.model, args.model)
     best_acc = {m: 0.0 for m in eval_pool}; best_std = {m: 0.0 for m in eval_pool}
     save_dir = os.path.join(args.save_path, "Baseline_DM", "%s_ipc%d_%s" % (args.dataset, args.ipc, args.lr_img))
-    out = open(args.log_file, "a") if (args.log_file and rank == 0) else None
-
-    def emit(rec):
-        if rank == 0:
-            line = json.dumps(rec)
-            (log.append(rec) if log is not None else None)
-            print(line, flush=True)
-            if out:
-                out.write(line + "\n"); out.flush()
-
-    eval_all = getattr(args, 'eval_ranks', 'rank0') == 'all' and not args.no_eval
+    log = driver.JsonLog(args.log_file, rank, log)
     eval_seed = None
-    if eval_all:
-        eval_seed = getattr(args, 'eval_seed', None)
-        if eval_seed is None:
-            box = [int(time.time() * 1000) % 100000 if rank == 0 else None]
-            if world > 1:
-                import torch.distributed as dist
-                dist.broadcast_object_list(box, src=0)
-            eval_seed = box[0]
-        emit({"eval_ranks": "all", "eval_seed": int(eval_seed), "world": world})
+    if args.eval_ranks == 'all' and not args.no_eval:          # (drawn and logged whether or not the data has test clips)
+        eval_seed = driver.draw_eval_seed(args.eval_seed, rank, world)
+        log.emit({"eval_ranks": "all", "eval_seed": eval_seed, "world": world})
+    label_syn = torch.arange(num_classes).repeat_interleave(args.ipc)
     eval_its = set(np.arange(0, args.Iteration + 1, args.eval_it).tolist())
     t0 = time.time()
     for it in range(args.Iteration + 1):
@@ -151,48 +110,22 @@ def run(args, backend=None, log=None):
             syn_all = trainer.gather_syn()
             trainer.sync()
             save_best = False
-            if eval_all and testloader is not None:
-                from . import evalpool
-                label_syn = torch.arange(num_classes).repeat_interleave(args.ipc)
-                eargs = argparse.Namespace(device=str(device), lr_net=args.lr_net, epoch_eval_train=args.epoch_eval_train,
-                                           batch_train=args.batch_train, model=args.model, eval_mode=args.eval_mode)
-                for model_eval in eval_pool:
-                    if model_eval != 'ConvNet3D':
-                        raise NotImplementedError("--eval_ranks all evaluates ConvNet3D (the hot path's network), not %s" % model_eval)
-                    make_net = evalpool.convnet3d_factory(num_classes, (args.im_size, args.im_size), args.frames)
-                    got = evalpool.evaluate_pool(make_net, syn_all.detach().clone(), label_syn, testloader, eargs, num_eval=args.num_eval,
-                                                 seed=int(eval_seed) + it, mode='none', rank=rank, world=world, num_classes=num_classes)
-                    mean, std = got["mean"], got["std"]           # (the same numbers on every rank: best_* stay in step)
-                    if mean > best_acc[model_eval]:
-                        best_acc[model_eval], best_std[model_eval], save_best = mean, std, True
-                    emit({"step": it, "Accuracy/%s" % model_eval: mean, "Max_Accuracy/%s" % model_eval: best_acc[model_eval],
-                          "Std/%s" % model_eval: std, "Max_Std/%s" % model_eval: best_std[model_eval]})
-                    emit({"step": it, "eval_pool": {"train_s": got["times"]["train_s"], "test_pass_s": got["times"]["test_pass_s"],
-                                                    "assignment": got["assignment"]}})
-            elif rank == 0 and testloader is not None:
-                label_syn = torch.arange(num_classes).repeat_interleave(args.ipc)
-                for model_eval in eval_pool:
-                    accs = []
-                    for it_eval in range(args.num_eval):
-                        net_eval = utils.get_network(model_eval, 3, num_classes, (args.im_size, args.im_size), frames=args.frames, dist=False).to(device)
-                        eargs = argparse.Namespace(device=str(device), lr_net=args.lr_net, epoch_eval_train=args.epoch_eval_train,
-                                                   batch_train=args.batch_train, model=args.model, eval_mode=args.eval_mode)
-                        _, _, acc_test, _ = utils.evaluate_synset(it_eval, net_eval, syn_all.detach().clone(), label_syn, testloader, eargs, mode='none')
-                        accs.append(acc_test)
-                    mean, std = float(np.mean(accs)), float(np.std(accs))
-                    if mean > best_acc[model_eval]:
-                        best_acc[model_eval], best_std[model_eval], save_best = mean, std, True
-                    emit({"step": it, "Accuracy/%s" % model_eval: mean, "Max_Accuracy/%s" % model_eval: best_acc[model_eval],
-                          "Std/%s" % model_eval: std, "Max_Std/%s" % model_eval: best_std[model_eval]})
+            if testloader is not None:
+                save_best, pooled = driver.evaluate_round(
+                    args, it, syn_all.detach().clone(), label_syn, 'none', args.lr_net, testloader, eval_pool, best_acc, best_std, log,
+                    rank=rank, world=world, device=device, num_classes=num_classes,
+                    pool_seed=None if eval_seed is None else eval_seed + it)
+                for got in pooled:
+                    log.emit({"step": it, "eval_pool": {"train_s": got["times"]["train_s"], "test_pass_s": got["times"]["test_pass_s"],
+                                                        "assignment": got["assignment"]}})
             if rank == 0 and (save_best or it % 1000 == 0):
                 checkpoint.save_images(save_dir, it, syn_all, best=save_best)
         loss = trainer.global_loss(trainer.step(it, overlap=True))
         if it % 10 == 0 or it == args.Iteration:
             trainer.sync()
-            emit({"step": it, "Loss": float(loss) / num_classes, "elapsed_s": round(time.time() - t0, 3)})
+            log.emit({"step": it, "Loss": float(loss) / num_classes, "elapsed_s": round(time.time() - t0, 3)})
     trainer.sync()
-    if out:
-        out.close()
+    log.close()
     return trainer
 
 

@@ -18,7 +18,8 @@ visits every file, ``reference`` only the first of the shuffle, as the reference
 ``vdt_`` kernels (include/vd_traj.h), ``off`` on torch expressions.  The walk is seeded (``--seed``) and the same on every rank;
 every rank holds all memories and takes its share of each student batch (distill.MTTTrainer).
 
-Data as ``run_dm`` (``--dataset synthetic``, the reference's frame folders, or ``--data_file f.pt``); the real training clips are
+Data as ``run_dm`` (``--dataset synthetic``, the reference's frame folders, or ``--data_file f.pt``; the test loaders, like the
+process setup, the log, the evaluation round and the project's own flags, are ``driver.py``'s); the real training clips are
 read for ``--memories images --init real`` only: ``ipc`` random clips per class, drawn from ``--seed`` -- no resident pool of
 the training set is built.  ``syn_lr`` starts at ``--lr_teacher`` and is trained only with ``--train_lr`` (``--lr_lr``);
 evaluation trains its networks with ``lr_net = float(syn_lr)`` of that iteration (distill_baseline.py:157,
@@ -37,12 +38,13 @@ Not here: the ``syn_{it}.png`` grid, wandb, evaluation architectures other than 
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import time
 
 import numpy as np
 import torch
+
+from . import driver
 
 # what the two parsers disagree on (distill_baseline.py:367-413, distill_s2d_ms.py:453-502)
 DEFAULTS = {
@@ -95,14 +97,8 @@ def build_parser(memories: str = "images"):
         p.add_argument('--n_hal', type=int, default=1, help='number of hallucinators (the first is trained)')
         p.add_argument('--startIt', type=int, default=0, help='first evaluation iteration')
     # the project's own
-    p.add_argument('--data_file', type=str, default=None)
-    p.add_argument('--im_size', type=int, default=112)
-    p.add_argument('--num_classes', type=int, default=50, help='synthetic data only')
-    p.add_argument('--log_file', type=str, default=None)
-    p.add_argument('--no_eval', action='store_true')
-    p.add_argument('--test_videos', type=str, default='host', choices=['host', 'resident'])
-    p.add_argument('--eval_ranks', type=str, default='rank0', choices=['rank0', 'all'])
-    p.add_argument('--eval_seed', type=int, default=None)
+    driver.add_data_flags(p)
+    driver.add_eval_flags(p)
     p.add_argument('--seed', type=int, default=0, help='seed of the expert walk, the noise memories, the real-clip draw and the hallucinators')
     p.add_argument('--expert_store', type=str, default='host', choices=['host', 'resident'],
                    help="host: one buffer file at a time in pinned host memory, two rows copied per iteration; resident: every "
@@ -123,8 +119,8 @@ def load_data(args, rank: int, device):
         from . import dataset as D
         _, _, num_classes, _, _, _, dst_train, dst_test, testloader = D.get_dataset(args.dataset, args.data_path,
                                                                                     img_size=(args.im_size, args.im_size))
-        if args.test_videos == 'resident' and (rank == 0 or args.eval_ranks == 'all') and not args.no_eval:
-            testloader = D.resident_loader(dst_test, device, batch_size=testloader.batch_size, workers=args.num_workers)
+        if not args.no_eval:
+            testloader = driver.folder_test_loader(args, rank, device, dst_test, testloader)
         return num_classes, (lambda idx: torch.stack([dst_train[int(i)][0] for i in idx])), list(dst_train.labels), testloader
     if args.data_file is None:
         C = args.num_classes
@@ -136,11 +132,8 @@ def load_data(args, rank: int, device):
     blob = torch.load(args.data_file, map_location="cpu")
     labels = blob["labels"].long()
     num_classes = int(labels.max()) + 1
-    test = None
-    if "test_clips" in blob:
-        test = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(blob["test_clips"].float(), blob["test_labels"].long()),
-                                           batch_size=64, shuffle=False)
-    return num_classes, (lambda idx: blob["clips"][torch.as_tensor(idx, dtype=torch.int64)].float()), labels.tolist(), test
+    return (num_classes, (lambda idx: blob["clips"][torch.as_tensor(idx, dtype=torch.int64)].float()), labels.tolist(),
+            driver.file_test_loader(blob))
 
 
 def real_init(clips_of, labels, num_classes: int, ipc: int, seed: int) -> torch.Tensor:
@@ -165,16 +158,7 @@ def run(args, ops=None, log=None):
     if args.buffer_path is None:
         raise ValueError("--buffer_path: the directory of the expert trajectories (replay_buffer_N.pt, written by "
                          "video_distillation_amd.buffer)")
-    rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    use_cuda = ops is None
-    device = torch.device("cuda", local_rank) if use_cuda else torch.device("cpu")
-    if use_cuda:
-        torch.cuda.set_device(device)
-    if world > 1:
-        import torch.distributed as dist
-        if not dist.is_initialized():
-            dist.init_process_group(backend="nccl" if use_cuda else "gloo")
+    rank, world, device = driver.start(use_cuda=ops is None)
     geo = plan.NetGeometry(args.frames, args.im_size, args.im_size)
     num_classes, clips_of, train_labels, testloader = load_data(args, rank, device)
     per_class = args.vpc if s2d else args.ipc
@@ -219,33 +203,18 @@ def run(args, ops=None, log=None):
         start_it = 0
     eval_pool = utils.get_eval_pool(args.eval_mode, args.model, args.model)
     best_acc = {m: 0.0 for m in eval_pool}; best_std = {m: 0.0 for m in eval_pool}
-    out = open(args.log_file, "a") if (args.log_file and rank == 0) else None
-
-    def emit(rec):
-        if rank == 0:
-            line = json.dumps(rec)
-            (log.append(rec) if log is not None else None)
-            print(line, flush=True)
-            if out:
-                out.write(line + "\n"); out.flush()
+    log = driver.JsonLog(args.log_file, rank, log)
 
     def sync():
         if device.type == "cuda":
             torch.cuda.synchronize(device)
 
     evaluate = not args.no_eval and testloader is not None
-    eval_all = args.eval_ranks == 'all' and evaluate
     eval_seed = None
-    if eval_all:
-        eval_seed = args.eval_seed
-        if eval_seed is None:
-            box = [int(time.time() * 1000) % 100000 if rank == 0 else None]
-            if world > 1:
-                import torch.distributed as dist
-                dist.broadcast_object_list(box, src=0)
-            eval_seed = box[0]
-        emit({"eval_ranks": "all", "eval_seed": int(eval_seed), "world": world})
-    emit({"expert_store": store.mode, "buffer_walk": store.walk, "buffer_files": len(store.files), "expert_epochs_per_trajectory": store.epochs,
+    if args.eval_ranks == 'all' and evaluate:
+        eval_seed = driver.draw_eval_seed(args.eval_seed, rank, world)
+        log.emit({"eval_ranks": "all", "eval_seed": eval_seed, "world": world})
+    log.emit({"expert_store": store.mode, "buffer_walk": store.walk, "buffer_files": len(store.files), "expert_epochs_per_trajectory": store.epochs,
           "fused_flat": getattr(ops, "flat", None) is not None, "batch_syn": batch_syn})
     test_freq = 200 if args.epoch_eval_train >= 200 else None          # (the reference's loop never tests below 200 epochs)
     eval_its = set(np.arange(start_it, args.Iteration + 1, args.eval_it).tolist())
@@ -256,8 +225,8 @@ def run(args, ops=None, log=None):
         sync()
         for it_, start_, grand_, lr_ in pending:
             g = float(grand_)
-            emit({"step": it_, "Grand_Loss": g, "Grand_Loss/%d" % start_: g, "Start_Epoch": start_, "Synthetic_LR": float(lr_),
-                  "elapsed_s": round(time.time() - t0, 3)})
+            log.emit({"step": it_, "Grand_Loss": g, "Grand_Loss/%d" % start_: g, "Start_Epoch": start_, "Synthetic_LR": float(lr_),
+                      "elapsed_s": round(time.time() - t0, 3)})
         del pending[:]
 
     for it in range(args.Iteration + 1):
@@ -269,41 +238,17 @@ def run(args, ops=None, log=None):
                 with torch.no_grad():          # the reference trains hals[0] only (:247) and evaluates / saves all n_hal
                     hals[0].encoder.weight.copy_(trainer.hal_w.view_as(hals[0].encoder.weight))
                     hals[0].encoder.bias.copy_(trainer.hal_b)
-                memories, labels_eval, mode = [static_all.detach().clone(), dynamic_all.detach().clone(), hals], None, 'multi-static'
-            else:
-                memories, labels_eval, mode = trainer.image_syn.detach().clone(), torch.arange(num_classes).repeat_interleave(args.ipc), 'none'
             save_this_it = False
-            if evaluate:
-                eargs = argparse.Namespace(device=str(device), lr_net=float(trainer.syn_lr), epoch_eval_train=args.epoch_eval_train,
-                                           batch_train=args.batch_train, model=args.model, eval_mode=args.eval_mode)
-                for model_eval in eval_pool:
-                    if eval_all:
-                        from . import evalpool
-                        if model_eval != 'ConvNet3D':
-                            raise NotImplementedError("--eval_ranks all evaluates ConvNet3D (the hot path's network), not %s" % model_eval)
-                        make_net = evalpool.convnet3d_factory(num_classes, hw, args.frames)
-                        got = evalpool.evaluate_pool(make_net, memories, labels_eval, testloader, eargs, num_eval=args.num_eval,
-                                                     seed=int(eval_seed) + it, mode=mode, rank=rank, world=world,
-                                                     num_classes=num_classes)
-                        mean, std = got["mean"], got["std"]           # (the same numbers on every rank: best_* stay in step)
-                    elif rank == 0:
-                        accs = []
-                        for it_eval in range(args.num_eval):
-                            net_eval = utils.get_network(model_eval, 3, num_classes, hw, frames=args.frames, dist=False).to(device)
-                            if s2d:
-                                _, _, acc_test, _ = utils.evaluate_synset(it_eval, net_eval, memories, None, testloader, eargs,
-                                                                          mode='multi-static')
-                            else:
-                                _, _, acc_test, _ = utils.evaluate_synset(it_eval, net_eval, memories.clone(), labels_eval, testloader,
-                                                                          eargs, mode='none', test_freq=test_freq)
-                            accs.append(acc_test)
-                        mean, std = float(np.mean(accs)), float(np.std(accs))
-                    else:
-                        continue
-                    if mean > best_acc[model_eval]:
-                        best_acc[model_eval], best_std[model_eval], save_this_it = mean, std, True
-                    emit({"step": it, "Accuracy/%s" % model_eval: mean, "Max_Accuracy/%s" % model_eval: best_acc[model_eval],
-                          "Std/%s" % model_eval: std, "Max_Std/%s" % model_eval: best_std[model_eval]})
+            if evaluate:          # networks trained with the syn_lr of this iteration; images test every 200 epochs
+                if s2d:
+                    memories, labels_eval, mode = [static_all.detach().clone(), dynamic_all.detach().clone(), hals], None, 'multi-static'
+                else:
+                    memories, labels_eval, mode = trainer.image_syn.detach().clone(), label_syn, 'none'
+                save_this_it, _ = driver.evaluate_round(
+                    args, it, memories, labels_eval, mode, float(trainer.syn_lr), testloader, eval_pool, best_acc, best_std, log,
+                    rank=rank, world=world, device=device, num_classes=num_classes,
+                    pool_seed=None if eval_seed is None else eval_seed + it, test_freq=None if s2d else test_freq)
+                del memories
             if rank == 0 and (save_this_it or it % 1000 == 0):
                 if s2d:
                     checkpoint.save_s2d(save_dir, it, dynamic_all, [h.encoder.weight for h in hals], [h.encoder.bias for h in hals],
@@ -312,15 +257,13 @@ def run(args, ops=None, log=None):
                         checkpoint.save_images(save_dir, it, static_all, best=save_this_it)
                 else:
                     checkpoint.save_images(save_dir, it, trainer.image_syn, best=save_this_it)
-            del memories
         lr_before = trainer.syn_lr
         grand = trainer.step(it, store.next())
         pending.append((it, trainer.last_start_epoch, grand, lr_before))
         if it % 10 == 0 or it == args.Iteration:
             flush()
     flush()
-    if out:
-        out.close()
+    log.close()
     return trainer
 
 

@@ -6,7 +6,8 @@ distill_s2d_ms.py:312-445, with its flag names and defaults for everything that 
         --vpc 1 --spc 2 --dpc 2 --lr_dynamic=1e-3 --lr_hal=1e-5
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m video_distillation_amd.run_s2d ...
 
-Data as ``run_dm`` (``--dataset synthetic``, the reference's frame folders, or ``--data_file f.pt``).  The static memory comes
+Data as ``run_dm`` (``run_dm.load_data``: ``--dataset synthetic``, the reference's frame folders, or ``--data_file f.pt``); process
+setup, log, evaluation round and the project's own flags are ``driver.py``'s.  The static memory comes
 from ``--path_static`` (a dict with key "image", (C*spc,3,H,W)) or seeded noise; the dynamic memory (C,dpc,T,1,H,W) is seeded
 noise drawn in full on the host, the same on every rank, of which the trainer keeps its classes -- every sharding starts from
 the same state.  ``n_hal`` hallucinators are created; as in the reference only the first is trained (``hal_idx = 0``,
@@ -23,13 +24,13 @@ Not here: the MTT branch (its driver is ``video_distillation_amd.run_mtt --memor
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import time
 
 import numpy as np
 import torch
 
+from . import driver
 from .run_dm import load_data
 
 
@@ -62,18 +63,12 @@ def build_parser():
     p.add_argument('--startIt', type=int, default=0, help='first evaluation iteration')
     p.add_argument('--save_path', type=str, default='./logged_files')
     p.add_argument('--seed', type=int, default=0, help='seed of the noise memories and of the hallucinators')
-    # run_dm's own
-    p.add_argument('--data_file', type=str, default=None)
-    p.add_argument('--im_size', type=int, default=112)
-    p.add_argument('--num_classes', type=int, default=50, help='synthetic data only')
+    # the project's own
     p.add_argument('--pool_per_class', type=int, default=93, help='synthetic data only')
     p.add_argument('--prec_real', type=str, default='f16')
     p.add_argument('--prec_syn', type=str, default='f16x3')
-    p.add_argument('--log_file', type=str, default=None)
-    p.add_argument('--no_eval', action='store_true')
-    p.add_argument('--test_videos', type=str, default='host', choices=['host', 'resident'])
-    p.add_argument('--eval_ranks', type=str, default='rank0', choices=['rank0', 'all'])
-    p.add_argument('--eval_seed', type=int, default=None)
+    driver.add_data_flags(p)
+    driver.add_eval_flags(p)
     return p
 
 
@@ -120,16 +115,7 @@ def initial_state(args, num_classes: int):
 def run(args, backend=None, log=None):
     from . import checkpoint, distill, plan, utils
     check_settings(args)
-    rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    use_cuda = backend is None
-    device = torch.device("cuda", local_rank) if use_cuda else torch.device("cpu")
-    if use_cuda:
-        torch.cuda.set_device(device)
-    if world > 1:
-        import torch.distributed as dist
-        if not dist.is_initialized():
-            dist.init_process_group(backend="nccl" if use_cuda else "gloo")
+    rank, world, device = driver.start(use_cuda=backend is None)
     geo = plan.NetGeometry(args.frames, args.im_size, args.im_size)
     pool, num_classes, _, testloader = load_data(args, rank, world, geo, device)
     if backend is None:
@@ -145,30 +131,12 @@ def run(args, backend=None, log=None):
     eval_pool = utils.get_eval_pool(args.eval_mode, args.model, args.model)
     best_acc = {m: 0.0 for m in eval_pool}; best_std = {m: 0.0 for m in eval_pool}
     save_dir = os.path.join(args.save_path, "S2D_multis_DM", "%s_ipc%d_%s_%s" % (args.dataset, args.vpc, args.lr_dynamic, args.lr_hal))
-    out = open(args.log_file, "a") if (args.log_file and rank == 0) else None
-
-    def emit(rec):
-        if rank == 0:
-            line = json.dumps(rec)
-            (log.append(rec) if log is not None else None)
-            print(line, flush=True)
-            if out:
-                out.write(line + "\n"); out.flush()
-
+    log = driver.JsonLog(args.log_file, rank, log)
     evaluate = not args.no_eval and testloader is not None
-    eval_all = args.eval_ranks == 'all' and evaluate
     eval_seed = None
-    if eval_all:
-        eval_seed = args.eval_seed
-        if eval_seed is None:
-            box = [int(time.time() * 1000) % 100000 if rank == 0 else None]
-            if world > 1:
-                import torch.distributed as dist
-                dist.broadcast_object_list(box, src=0)
-            eval_seed = box[0]
-        emit({"eval_ranks": "all", "eval_seed": int(eval_seed), "world": world})
-    eargs = argparse.Namespace(device=str(device), lr_net=args.lr_teacher, epoch_eval_train=args.epoch_eval_train,
-                               batch_train=args.batch_train, model=args.model, eval_mode=args.eval_mode)
+    if args.eval_ranks == 'all' and evaluate:
+        eval_seed = driver.draw_eval_seed(args.eval_seed, rank, world)
+        log.emit({"eval_ranks": "all", "eval_seed": eval_seed, "world": world})
     eval_its = set(np.arange(args.startIt, args.Iteration + 1, args.eval_it).tolist())
     t0 = time.time()
     for it in range(args.Iteration + 1):
@@ -179,33 +147,10 @@ def run(args, backend=None, log=None):
                 hals[0].encoder.bias.copy_(trainer.hal_b)
             save_this_it = False
             if evaluate:
-                memories = [static_all.detach().clone(), dynamic_all.detach().clone(), hals]
-                for model_eval in eval_pool:
-                    if eval_all:
-                        from . import evalpool
-                        if model_eval != 'ConvNet3D':
-                            raise NotImplementedError("--eval_ranks all evaluates ConvNet3D (the hot path's network), not %s" % model_eval)
-                        make_net = evalpool.convnet3d_factory(num_classes, (args.im_size, args.im_size), args.frames)
-                        got = evalpool.evaluate_pool(make_net, memories, None, testloader, eargs, num_eval=args.num_eval,
-                                                     seed=int(eval_seed) + it, mode='multi-static', rank=rank, world=world,
-                                                     num_classes=num_classes)
-                        mean, std = got["mean"], got["std"]           # (the same numbers on every rank: best_* stay in step)
-                    elif rank == 0:
-                        accs = []
-                        for it_eval in range(args.num_eval):
-                            net_eval = utils.get_network(model_eval, 3, num_classes, (args.im_size, args.im_size), frames=args.frames,
-                                                         dist=False).to(device)
-                            _, _, acc_test, _ = utils.evaluate_synset(it_eval, net_eval, memories, None, testloader, eargs,
-                                                                      mode='multi-static')
-                            accs.append(acc_test)
-                        mean, std = float(np.mean(accs)), float(np.std(accs))
-                    else:
-                        continue
-                    if mean > best_acc[model_eval]:
-                        best_acc[model_eval], best_std[model_eval], save_this_it = mean, std, True
-                    emit({"step": it, "Accuracy/%s" % model_eval: mean, "Max_Accuracy/%s" % model_eval: best_acc[model_eval],
-                          "Std/%s" % model_eval: std, "Max_Std/%s" % model_eval: best_std[model_eval]})
-                del memories
+                save_this_it, _ = driver.evaluate_round(
+                    args, it, [static_all.detach().clone(), dynamic_all.detach().clone(), hals], None, 'multi-static', args.lr_teacher,
+                    testloader, eval_pool, best_acc, best_std, log, rank=rank, world=world, device=device, num_classes=num_classes,
+                    pool_seed=None if eval_seed is None else eval_seed + it)
             if rank == 0 and (save_this_it or it % 1000 == 0):
                 checkpoint.save_s2d(save_dir, it, dynamic_all, [h.encoder.weight for h in hals], [h.encoder.bias for h in hals],
                                     best=save_this_it)
@@ -214,10 +159,9 @@ def run(args, backend=None, log=None):
         loss = trainer.global_loss(trainer.step(it, overlap=True))
         if it % 10 == 0 or it == args.Iteration:
             trainer.sync()
-            emit({"step": it, "Loss": float(loss) / num_classes, "elapsed_s": round(time.time() - t0, 3)})
+            log.emit({"step": it, "Loss": float(loss) / num_classes, "elapsed_s": round(time.time() - t0, 3)})
     trainer.sync()
-    if out:
-        out.close()
+    log.close()
     return trainer
 
 
