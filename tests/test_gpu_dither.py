@@ -186,7 +186,7 @@ def test_last_level_in_hi_lo_pairs(geom, n):
     e1 = engine.EmbedEngine(geo, prec="f16", chunk=4096); e1.set_weights(w)
     e3 = engine.EmbedEngine(geo, prec="f16", chunk=4096, last_hilo=True); e3.set_weights(w)
     f1, f3 = e1.forward(x.cuda()), e3.forward(x.cuda())
-    per2 = int(np.prod(e3.fwd[1].plan.out_shape[:-1]))
+    per2 = e3.per2
     hi3 = e3._ws["act2"][:2 * n * per2 * 8].view(2, n * per2, 8)[0].clone()
     lo3 = e3._ws["act2"][:2 * n * per2 * 8].view(2, n * per2, 8)[1].clone()
     hi1 = e1._ws["act2"][:n * per2 * 8].view(n * per2, 8)

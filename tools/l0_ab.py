@@ -20,13 +20,13 @@ for v in variants:
 e5 = engs["5"]
 L = hip.lib(); st = hip.stream_ptr(e5.device)
 x = torch.randn(64, 16, 3, 112, 112, device="cuda")
-n_slots0 = nclips * 16 * 3 * 112 * 15
+n_slots0 = nclips * e5.per0
 slots0 = torch.empty((1, n_slots0, 8), dtype=torch.int16, device="cuda")
-per = 64 * 16 * 3 * 112 * 15
+per = 64 * e5.per0
 for k in range(0, nclips, 64):       # 64 distinct clips, repeated
     m = min(64, nclips - k)
     L.vd_pix2rows(hip.ptr(x), None, m, 16, 112, 112, slots0.data_ptr() + k // 64 * per * 16, None, e5.prec, st)
-n1 = nclips * int(np.prod(e5.fwd[0].plan.out_shape[:-1]))
+n1 = nclips * e5.per1
 outs = {v: torch.empty((1, n1, 8), dtype=torch.int16, device="cuda") for v in engs}
 times = {v: [] for v in engs}
 for r in range(reps + 2):

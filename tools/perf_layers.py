@@ -26,11 +26,8 @@ for prec in precs:
     # per-layer: re-run individual stages
     L = hip.lib(); st = hip.stream_ptr(eng.device)
     g = geo
-    import numpy as np
-    n_slots0 = nclips*16*3*112*15
-    slots0 = eng._buf("slots0", (eng.planes, n_slots0, 8), torch.int16)
-    n1 = nclips*int(np.prod(eng.fwd[0].plan.out_shape[:-1])); act1 = eng._buf("act1", (eng.planes, n1, 8), torch.int16)
-    n2 = nclips*int(np.prod(eng.fwd[1].plan.out_shape[:-1])); act2 = eng._buf("act2", (eng.planes, n2, 8), torch.int16)
+    n_slots0, n1, n2 = nclips * eng.per0, nclips * eng.per1, nclips * eng.per2
+    slots0, (act1, act2) = eng.rows_buf(nclips), eng.act_bufs(nclips)
     feats = torch.empty(nclips, 2048, device="cuda")
     def t(fn, reps=3):
         fn(); torch.cuda.synchronize()

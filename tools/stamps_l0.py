@@ -25,10 +25,8 @@ for _ in range(3):        # (sustained clocks)
     eng.forward(x)
 torch.cuda.synchronize()
 buf.zero_()
-import numpy as _np
-n_slots0 = nclips * 16 * 3 * 112 * 15
-slots0 = eng._buf("slots0", (eng.planes, n_slots0, 8), torch.int16)
-n1 = nclips * int(_np.prod(dp.plan.out_shape[:-1])); act1 = eng._buf("act1", (eng.planes, n1, 8), torch.int16)
+n_slots0, n1 = nclips * eng.per0, nclips * eng.per1
+slots0, (act1, _) = eng.rows_buf(nclips), eng.act_bufs(nclips)
 e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
 e0.record()
 dp.run(slots0, n_slots0, eng._weights[1], act1.data_ptr(), n1, None, nclips)

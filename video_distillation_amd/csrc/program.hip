@@ -218,14 +218,42 @@ extern "C" int vd_embed_create(int frames, int height, int width, int prec, int 
 
 extern "C" int64_t vd_embed_num_features(const VdEmbed* e) { return e ? e->nfeat : -1; }
 
-extern "C" int64_t vd_embed_workspace_bytes(const VdEmbed* e, int64_t nclips) {
-    if (e == nullptr || nclips < 0) return -1;
-    return (int64_t)e->planes * nclips * (e->slots0_per_clip + e->slots1_per_clip + e->slots2_per_clip) * 16 + 3 * 256;
-}
+static char* align256(char* p) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255); }
 
-extern "C" int64_t vd_embed_argmax_bytes(const VdEmbed* e, int64_t nclips) {
-    if (e == nullptr || nclips < 0) return -1;
-    return nclips * (e->slots1_per_clip * 8 + e->slots2_per_clip * 8 + e->nfeat) + 3 * 256;
+// Walks a caller's workspace region by region.  With a base pointer it places each region at the next 256-byte boundary; with or
+// without one it adds up what the regions need (256 bytes of alignment slack each): a size query and a carve-out are the SAME walk.
+struct Carve {
+    char* p;
+    int64_t bytes;
+    char* take(int64_t n) {
+        bytes += n + 256;
+        if (p == nullptr) return nullptr;
+        char* at = align256(p);
+        p = at + n;
+        return at;
+    }
+};
+
+struct FwdLayout {        // forward workspace of B clips (pixel rows, kept activations of levels 0 / 1) and the arg-max block
+    char* rows; char* act[3];
+    int64_t act_plane[3], n0, n1, n2, bytes;
+    uint8_t* am[3];
+    int64_t am_bytes;
+};
+
+static FwdLayout fwd_layout(const VdEmbed* e, int64_t B, void* workspace, const void* argmax) {
+    FwdLayout L = {};
+    L.n0 = B * e->slots0_per_clip; L.n1 = B * e->slots1_per_clip; L.n2 = B * e->slots2_per_clip;
+    Carve w = {static_cast<char*>(workspace), 0}, a = {const_cast<char*>(static_cast<const char*>(argmax)), 0};
+    L.rows = w.take((int64_t)e->planes * L.n0 * 16);
+    L.act[1] = w.take((int64_t)e->planes * L.n1 * 16);
+    L.act[2] = w.take((int64_t)e->planes * L.n2 * 16);
+    L.act_plane[1] = L.n1; L.act_plane[2] = L.n2;
+    L.am[0] = reinterpret_cast<uint8_t*>(a.take(L.n1 * 8));
+    L.am[1] = reinterpret_cast<uint8_t*>(a.take(L.n2 * 8));
+    L.am[2] = reinterpret_cast<uint8_t*>(a.take(B * e->nfeat));
+    L.bytes = w.bytes; L.am_bytes = a.bytes;
+    return L;
 }
 
 static int64_t dy_slots(const VdEmbed* e, int l, int64_t nclips) {
@@ -233,13 +261,35 @@ static int64_t dy_slots(const VdEmbed* e, int l, int64_t nclips) {
     return nclips * (d[1] / 8) * (int64_t)d[5] * d[6] * d[7];
 }
 
+static int64_t dx_elems(const VdEmbed* e, int l, int64_t nclips) { return nclips * (int64_t)e->dims[l][2] * e->dims[l][3] * e->dims[l][4] * e->dims[l][0]; }
+
+struct BwdLayout {        // backward workspace of B clips: one dense dy region (the largest level's), the fp32 input gradients of levels 2 / 1, scales
+    char* dy; char* dxbuf[3];
+    float* scale;         // 12 floats in a 256-byte block
+    int64_t dymax, bytes;
+};
+
+static BwdLayout bwd_layout(const VdEmbed* e, int64_t B, void* workspace) {
+    BwdLayout L = {};
+    for (int l = 0; l < 3; ++l) L.dymax = std::max(L.dymax, dy_slots(e, l, B));
+    Carve w = {static_cast<char*>(workspace), 0};
+    L.dy = w.take((int64_t)e->planes_bwd * L.dymax * 16);
+    for (int l = 1; l < 3; ++l) L.dxbuf[l] = w.take(dx_elems(e, l, B) * 4);
+    L.scale = reinterpret_cast<float*>(w.take(256));
+    L.bytes = w.bytes;
+    return L;
+}
+
+extern "C" int64_t vd_embed_workspace_bytes(const VdEmbed* e, int64_t nclips) {
+    return (e == nullptr || nclips < 0) ? -1 : fwd_layout(e, nclips, nullptr, nullptr).bytes;
+}
+
+extern "C" int64_t vd_embed_argmax_bytes(const VdEmbed* e, int64_t nclips) {
+    return (e == nullptr || nclips < 0) ? -1 : fwd_layout(e, nclips, nullptr, nullptr).am_bytes;
+}
+
 extern "C" int64_t vd_embed_backward_workspace_bytes(const VdEmbed* e, int64_t nclips) {
-    if (e == nullptr || nclips < 0 || e->prec_bwd < 0) return -1;
-    int64_t dy = 0;
-    for (int l = 0; l < 3; ++l) dy = dy > dy_slots(e, l, nclips) ? dy : dy_slots(e, l, nclips);
-    int64_t dx = 0;
-    for (int l = 1; l < 3; ++l) dx += nclips * (int64_t)e->dims[l][2] * e->dims[l][3] * e->dims[l][4] * e->dims[l][0] * 4;
-    return (int64_t)e->planes_bwd * dy * 16 + dx + 5 * 256;       // four 256-byte alignments + the 12 scale floats behind the last one
+    return (e == nullptr || nclips < 0 || e->prec_bwd < 0) ? -1 : bwd_layout(e, nclips, nullptr).bytes;
 }
 
 extern "C" int vd_embed_set_weights(VdEmbed* e, const float* w0, const float* b0, const float* w1, const float* b1,
@@ -256,29 +306,18 @@ extern "C" int vd_embed_set_weights(VdEmbed* e, const float* w0, const float* b0
     return 0;
 }
 
-static char* align256(char* p) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255); }
-
 static int embed_forward_impl(VdEmbed* e, const float* clips, const int64_t* clip_index, int64_t nclips, void* workspace,
                               int64_t workspace_bytes, float* features, uint8_t* argmax, void* stream) {
     if (e == nullptr || clips == nullptr || features == nullptr || nclips < 0 || nclips > 0x7fffffff) return -1;
     if (!e->has_weights) return -6;
     if (nclips == 0) return 0;
-    if (workspace == nullptr || workspace_bytes < vd_embed_workspace_bytes(e, nclips)) return -7;
-    const int64_t n0 = nclips * e->slots0_per_clip, n1 = nclips * e->slots1_per_clip, n2 = nclips * e->slots2_per_clip;
-    char* rows = align256(static_cast<char*>(workspace));
-    char* act1 = align256(rows + (int64_t)e->planes * n0 * 16);
-    char* act2 = align256(act1 + (int64_t)e->planes * n1 * 16);
-    uint8_t *am0 = nullptr, *am1 = nullptr, *am2 = nullptr;
-    if (argmax != nullptr) {
-        am0 = reinterpret_cast<uint8_t*>(align256(reinterpret_cast<char*>(argmax)));
-        am1 = reinterpret_cast<uint8_t*>(align256(reinterpret_cast<char*>(am0) + n1 * 8));
-        am2 = reinterpret_cast<uint8_t*>(align256(reinterpret_cast<char*>(am1) + n2 * 8));
-    }
-    int rc = vd_pix2rows(clips, clip_index, nclips, e->frames, e->height, e->width, rows, e->planes == 2 ? rows + n0 * 16 : nullptr,
+    const FwdLayout L = fwd_layout(e, nclips, workspace, argmax);
+    if (workspace == nullptr || workspace_bytes < L.bytes) return -7;
+    int rc = vd_pix2rows(clips, clip_index, nclips, e->frames, e->height, e->width, L.rows, e->planes == 2 ? L.rows + L.n0 * 16 : nullptr,
                          e->prec, stream);
-    if (rc == 0) rc = vd_program_run(e->prog[0], rows, n0, e->bias[0], act1, n1, am0, nullptr, (int)nclips, stream);
-    if (rc == 0) rc = vd_program_run(e->prog[1], act1, n1, e->bias[1], act2, n2, am1, nullptr, (int)nclips, stream);
-    if (rc == 0) rc = vd_program_run(e->prog[2], act2, n2, e->bias[2], features, 0, am2, nullptr, (int)nclips, stream);
+    if (rc == 0) rc = vd_program_run(e->prog[0], L.rows, L.n0, e->bias[0], L.act[1], L.n1, L.am[0], nullptr, (int)nclips, stream);
+    if (rc == 0) rc = vd_program_run(e->prog[1], L.act[1], L.n1, e->bias[1], L.act[2], L.n2, L.am[1], nullptr, (int)nclips, stream);
+    if (rc == 0) rc = vd_program_run(e->prog[2], L.act[2], L.n2, e->bias[2], features, 0, L.am[2], nullptr, (int)nclips, stream);
     return rc;
 }
 
@@ -293,55 +332,49 @@ extern "C" int vd_embed_forward_keep(VdEmbed* e, const float* clips, const int64
     return embed_forward_impl(e, clips, clip_index, nclips, workspace, workspace_bytes, features, argmax, stream);
 }
 
-// d <g_features, embed(clips)> / d clips for a vd_embed_forward_keep call (same weights): per level, last to first,
-// un-pool + ReLU backward into dense dy slots (power-of-two scaled for the fp16 formats), then the level's dgrad programs
+// One level of the backward pass: the power-of-two scale of the incoming gradient into scale[4 l ..] (fp16 formats), then -- unless
+// `dense` is off -- ReLU + un-pool backward into the dense dy slots, `between(scale of this level or NULL)` (the parameter side of
+// a training step), and the level's input-gradient programs into `out`, which becomes the next level's gradient (layout 1).
+template <class Between>
+static int level_backward(const VdEmbed* e, int l, int64_t B, const uint8_t* am, char* dy, float* scale, bool dense, float* out,
+                          const float*& grad, int64_t& grad_n, int& layout, void* stream, Between between) {
+    const int* d = e->dims[l];
+    const int64_t nslots = dy_slots(e, l, B);
+    float* sc = nullptr;
+    int rc = 0;
+    if (e->prec_bwd == VD_PREC_F16 || e->prec_bwd == VD_PREC_F16X3) {
+        sc = scale + 4 * l;
+        if ((rc = vd_absmax_scale(grad, grad_n, 1024.0f, sc, stream))) return rc;
+    }
+    if (dense) rc = vd_unpool_relu_bwd(grad, am, B, d[1], d[8], d[9], d[10], d[11], d[5], d[6], d[7], layout, dy,
+                                       e->planes_bwd == 2 ? dy + nslots * 16 : nullptr, e->prec_bwd, sc, stream);
+    if (rc == 0) rc = between(sc);
+    if (rc || !dense) return rc;
+    for (int c = 0; c < e->nbwd[l]; ++c)
+        if ((rc = vd_program_run_scaled(e->bwd[l][c], dy, nslots, nullptr, out, 0, nullptr, nullptr, (int)B, sc ? sc + 1 : nullptr, stream))) return rc;
+    grad = out;
+    grad_n = dx_elems(e, l, B);
+    layout = 1;
+    return 0;
+}
+
+// d <g_features, embed(clips)> / d clips for a vd_embed_forward_keep call (same weights): level_backward, last level to first
 extern "C" int vd_embed_backward(VdEmbed* e, const float* g_features, const uint8_t* argmax, int64_t nclips, void* workspace,
                                  int64_t workspace_bytes, float* g_clips, void* stream) {
     if (e == nullptr || g_features == nullptr || argmax == nullptr || g_clips == nullptr || nclips < 0 || nclips > 0x7fffffff) return -1;
     if (e->prec_bwd < 0) return -8;
     if (!e->has_weights) return -6;
     if (nclips == 0) return 0;
-    if (workspace == nullptr || workspace_bytes < vd_embed_backward_workspace_bytes(e, nclips)) return -7;
-    const int64_t n1 = nclips * e->slots1_per_clip, n2 = nclips * e->slots2_per_clip;
-    const uint8_t* am[3];
-    am[0] = reinterpret_cast<const uint8_t*>(align256(const_cast<char*>(reinterpret_cast<const char*>(argmax))));
-    am[1] = reinterpret_cast<const uint8_t*>(align256(const_cast<char*>(reinterpret_cast<const char*>(am[0])) + n1 * 8));
-    am[2] = reinterpret_cast<const uint8_t*>(align256(const_cast<char*>(reinterpret_cast<const char*>(am[1])) + n2 * 8));
-    int64_t dymax = 0;
-    for (int l = 0; l < 3; ++l) dymax = dymax > dy_slots(e, l, nclips) ? dymax : dy_slots(e, l, nclips);
-    char* dy = align256(static_cast<char*>(workspace));
-    char* dxbuf[3] = {nullptr, nullptr, nullptr};
-    char* cur = align256(dy + (int64_t)e->planes_bwd * dymax * 16);
-    for (int l = 1; l < 3; ++l) {
-        dxbuf[l] = cur;
-        cur = align256(cur + nclips * (int64_t)e->dims[l][2] * e->dims[l][3] * e->dims[l][4] * e->dims[l][0] * 4);
-    }
-    float* scale = reinterpret_cast<float*>(cur);
-    const bool scaled = (e->prec_bwd == VD_PREC_F16 || e->prec_bwd == VD_PREC_F16X3);
+    const BwdLayout W = bwd_layout(e, nclips, workspace);
+    if (workspace == nullptr || workspace_bytes < W.bytes) return -7;
+    const FwdLayout L = fwd_layout(e, nclips, nullptr, argmax);
     const float* grad = g_features;
     int64_t grad_n = nclips * e->nfeat;
     int layout = 0;
     for (int l = 2; l >= 0; --l) {
-        const int* d = e->dims[l];
-        const int64_t nslots = dy_slots(e, l, nclips);
-        float* sc = nullptr;
-        int rc = 0;
-        if (scaled) {
-            sc = scale + 4 * l;
-            rc = vd_absmax_scale(grad, grad_n, 1024.0f, sc, stream);
-            if (rc) return rc;
-        }
-        rc = vd_unpool_relu_bwd(grad, am[l], nclips, d[1], d[8], d[9], d[10], d[11], d[5], d[6], d[7], layout, dy,
-                                e->planes_bwd == 2 ? dy + nslots * 16 : nullptr, e->prec_bwd, sc, stream);
+        float* out = (l == 0) ? g_clips : reinterpret_cast<float*>(W.dxbuf[l]);
+        const int rc = level_backward(e, l, nclips, L.am[l], W.dy, W.scale, true, out, grad, grad_n, layout, stream, [](float*) { return 0; });
         if (rc) return rc;
-        float* outp = (l == 0) ? g_clips : reinterpret_cast<float*>(dxbuf[l]);
-        for (int c = 0; c < e->nbwd[l]; ++c) {
-            rc = vd_program_run_scaled(e->bwd[l][c], dy, nslots, nullptr, outp, 0, nullptr, nullptr, (int)nclips, sc ? sc + 1 : nullptr, stream);
-            if (rc) return rc;
-        }
-        grad = outp;
-        grad_n = nclips * (int64_t)d[2] * d[3] * d[4] * d[0];
-        layout = 1;
     }
     return 0;
 }
@@ -484,28 +517,9 @@ extern "C" int vd_train_step(VdTrain* t, float* const* params, float* const* mom
     rc = (t->ordered ? vd_head_train_bwd_ordered : vd_head_train_bwd)(dlog, amt, dropped, dropout_mask, params[6], B, d2[1], d2[8], d2[9],
                                                                       d2[10], t->kt, t->kh, t->kw, t->K, g[6], g[7], g_feat, stream);
     if (rc) return rc;
-    // kept activations and arg-max bytes: the layout of embed_forward_impl
-    const int64_t n0 = B * e->slots0_per_clip, n1 = B * e->slots1_per_clip, n2 = B * e->slots2_per_clip;
-    char* rows = align256(ws + L.fwd);
-    char* act[3] = {nullptr, align256(rows + (int64_t)e->planes * n0 * 16), nullptr};
-    act[2] = align256(act[1] + (int64_t)e->planes * n1 * 16);
-    const int64_t act_plane[3] = {0, n1, n2};
-    const uint8_t* am[3];
-    am[0] = reinterpret_cast<const uint8_t*>(align256(reinterpret_cast<char*>(argmax)));
-    am[1] = reinterpret_cast<const uint8_t*>(align256(const_cast<char*>(reinterpret_cast<const char*>(am[0])) + n1 * 8));
-    am[2] = reinterpret_cast<const uint8_t*>(align256(const_cast<char*>(reinterpret_cast<const char*>(am[1])) + n2 * 8));
-    // dense dy + dx buffers: the layout of vd_embed_backward
-    int64_t dymax = 0;
-    for (int l = 0; l < 3; ++l) dymax = std::max(dymax, dy_slots(e, l, B));
-    char* dy = align256(ws + L.bwd);
-    char* dxbuf[3] = {nullptr, nullptr, nullptr};
-    char* cur = align256(dy + (int64_t)e->planes_bwd * dymax * 16);
-    for (int l = 1; l < 3; ++l) {
-        dxbuf[l] = cur;
-        cur = align256(cur + B * (int64_t)e->dims[l][2] * e->dims[l][3] * e->dims[l][4] * e->dims[l][0] * 4);
-    }
+    const FwdLayout F = fwd_layout(e, B, ws + L.fwd, argmax);      // kept activations and arg-max bytes, where the forward put them
+    const BwdLayout W = bwd_layout(e, B, ws + L.bwd);
     float* scale = reinterpret_cast<float*>(ws + L.scale);
-    const bool scaled = (e->prec_bwd == VD_PREC_F16 || e->prec_bwd == VD_PREC_F16X3);
     char* xT = ws + L.xT;
     char* bp = ws + L.bp;
     float* copies = reinterpret_cast<float*>(ws + L.copies);
@@ -515,45 +529,31 @@ extern "C" int vd_train_step(VdTrain* t, float* const* params, float* const* mom
     for (int l = 2; l >= 0; --l) {
         const int* d = e->dims[l];
         const int cin = d[0], cout = d[1];
-        const int64_t nslots = dy_slots(e, l, B), CCb = (B + 7) / 8, npos_in = (int64_t)d[2] * d[3] * d[4];
-        float* sc = nullptr;
-        if (scaled) {
-            sc = scale + 4 * l;
-            if ((rc = vd_absmax_scale(grad, grad_n, 1024.0f, sc, stream))) return rc;
-        }
-        if (l > 0) {
-            rc = vd_unpool_relu_bwd(grad, am[l], B, cout, d[8], d[9], d[10], d[11], d[5], d[6], d[7], layout, dy,
-                                    e->planes_bwd == 2 ? dy + nslots * 16 : nullptr, e->prec_bwd, sc, stream);
-            if (rc) return rc;
-        }
-        if (t->ordered) rc = vd_bias_grad_pooled_ordered(grad, am[l], B, cout, (int64_t)d[8] * d[9] * d[10], layout,
-                                                         reinterpret_cast<float*>(ws + L.bias_part), g[2 * l + 1], stream);
-        else rc = vd_bias_grad_pooled(grad, am[l], B, cout, (int64_t)d[8] * d[9] * d[10], layout, g[2 * l + 1], stream);
-        if (rc) return rc;
-        // weight gradient: x clip-minor, dy packed straight from the pooled gradient, boxes accumulate into copies
-        const int64_t xT_plane = (int64_t)cin * CCb * npos_in;
-        if (l == 0) rc = vd_clip_minor_pix(clips, B, d[2], d[3], d[4], xT, e->planes_bwd == 2 ? xT + xT_plane * 16 : nullptr, e->prec_bwd, stream);
-        else rc = vd_clip_minor_cl(act[l], act_plane[l], e->planes_bwd, B, cin, npos_in, xT, xT_plane, stream);
-        if (rc) return rc;
-        const int nt = t->block[l][0], noh = t->block[l][1], now = t->block[l][2];
-        const int64_t nbox = (int64_t)((d[5] + nt - 1) / nt) * ((d[6] + noh - 1) / noh) * ((d[7] + now - 1) / now);
-        const int64_t bp_elems = nbox * CCb * (nt * noh * now / 2) * (cout / 32) * 64 * 8;
-        rc = vd_unpool_relu_bwd_packed(grad, am[l], B, cout, d[8], d[9], d[10], d[11], d[5], d[6], d[7], layout, nt, noh, now, bp,
-                                       e->planes_bwd == 2 ? bp + bp_elems * 2 : nullptr, e->prec_bwd, sc, stream);
-        if (rc) return rc;
-        const int64_t copy_elems = (int64_t)cin * 147 * cout;
-        if (hipMemsetAsync(copies, 0, (size_t)t->replicas[l] * copy_elems * 4, st) != hipSuccess) return -9;
-        rc = vd_program_run_wgrad(t->wg[l], xT, xT_plane, bp, bp_elems, copies, copy_elems, cin, sc ? sc + 1 : nullptr, stream);
-        if (rc == 0) rc = vd_replica_sum(copies, t->replicas[l], cin * 147, cout, g[2 * l], stream);
-        if (rc) return rc;
-        if (l > 0) {
-            float* outp = reinterpret_cast<float*>(dxbuf[l]);
-            for (int c = 0; c < e->nbwd[l]; ++c)
-                if ((rc = vd_program_run_scaled(e->bwd[l][c], dy, nslots, nullptr, outp, 0, nullptr, nullptr, (int)B, sc ? sc + 1 : nullptr, stream))) return rc;
-            grad = outp;
-            grad_n = B * npos_in * cin;
-            layout = 1;
-        }
+        const int64_t CCb = (B + 7) / 8, npos_in = (int64_t)d[2] * d[3] * d[4];
+        // the parameter side, between the level's un-pool and its input-gradient programs (level 0: no dense dy, no input gradient)
+        auto param_side = [&](float* sc) {
+            int r;
+            if (t->ordered) r = vd_bias_grad_pooled_ordered(grad, F.am[l], B, cout, (int64_t)d[8] * d[9] * d[10], layout,
+                                                             reinterpret_cast<float*>(ws + L.bias_part), g[2 * l + 1], stream);
+            else r = vd_bias_grad_pooled(grad, F.am[l], B, cout, (int64_t)d[8] * d[9] * d[10], layout, g[2 * l + 1], stream);
+            if (r) return r;
+            // weight gradient: x clip-minor, dy packed straight from the pooled gradient, boxes accumulate into copies
+            const int64_t xT_plane = (int64_t)cin * CCb * npos_in;
+            if (l == 0) r = vd_clip_minor_pix(clips, B, d[2], d[3], d[4], xT, e->planes_bwd == 2 ? xT + xT_plane * 16 : nullptr, e->prec_bwd, stream);
+            else r = vd_clip_minor_cl(F.act[l], F.act_plane[l], e->planes_bwd, B, cin, npos_in, xT, xT_plane, stream);
+            if (r) return r;
+            const int nt = t->block[l][0], noh = t->block[l][1], now = t->block[l][2];
+            const int64_t nbox = (int64_t)((d[5] + nt - 1) / nt) * ((d[6] + noh - 1) / noh) * ((d[7] + now - 1) / now);
+            const int64_t bp_elems = nbox * CCb * (nt * noh * now / 2) * (cout / 32) * 64 * 8;
+            r = vd_unpool_relu_bwd_packed(grad, F.am[l], B, cout, d[8], d[9], d[10], d[11], d[5], d[6], d[7], layout, nt, noh, now, bp,
+                                           e->planes_bwd == 2 ? bp + bp_elems * 2 : nullptr, e->prec_bwd, sc, stream);
+            if (r) return r;
+            const int64_t copy_elems = (int64_t)cin * 147 * cout;
+            if (hipMemsetAsync(copies, 0, (size_t)t->replicas[l] * copy_elems * 4, st) != hipSuccess) return -9;
+            r = vd_program_run_wgrad(t->wg[l], xT, xT_plane, bp, bp_elems, copies, copy_elems, cin, sc ? sc + 1 : nullptr, stream);
+            return r ? r : vd_replica_sum(copies, t->replicas[l], cin * 147, cout, g[2 * l], stream);
+        };
+        if ((rc = level_backward(e, l, B, F.am[l], W.dy, scale, l > 0, reinterpret_cast<float*>(W.dxbuf[l]), grad, grad_n, layout, stream, param_side))) return rc;
     }
     for (int i = 0; i < 8; ++i)
         if ((rc = vd_sgd_momentum_wd(params[i], momentum[i], g[i], L.gsz[i], lr, mom, weight_decay, first, stream))) return rc;

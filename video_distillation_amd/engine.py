@@ -8,6 +8,7 @@ parameters that are frozen (distill_baseline.py:336-337).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import threading
 import os
@@ -307,6 +308,13 @@ def round_weights(params: Sequence[torch.Tensor], prec: str, levels: Sequence[in
     return out
 
 
+def clip_slots(geo: P.NetGeometry, fwd_plans: Sequence[P.ConvPlan]) -> Tuple[int, int, int]:
+    """16-byte slots per clip of the three activation levels: the padded 16-bit pixel rows, then what forward levels 0 and 1
+    write (channels-last slots) -- the one place the workspaces of every call path below are sized from."""
+    per0 = geo.frames * 3 * geo.height * (P.pix_row_pitch(geo.width) // 8)
+    return (per0,) + tuple(int(np.prod(pl.out_shape[:-1])) for pl in fwd_plans[:2])
+
+
 class EmbedEngine:
     def __init__(self, geo: P.NetGeometry, prec: str = "bf16x3", device="cuda:0", chunk: int = 256,
                  prec_bwd: Optional[str] = None, ntw0: Optional[int] = None, batch_hint: Optional[int] = None,
@@ -336,6 +344,7 @@ class EmbedEngine:
         self.batch_hint = batch_hint      # typical clips per launch: small batches get latency-oriented programs
         net = P.plan_network(geo, ntw=self.ntw, ntw0=ntw0, balanced=bal, batch_hint=batch_hint, bwd0_small=bwd0_small)
         self.dims = net["dims"]
+        self.per0, self.per1, self.per2 = clip_slots(geo, net["fwd"])
         self.fwd = [_DevPlan(pl, self.device, self.prec) for pl in net["fwd"]]
         self.fwd2x = None
         self.last_c8 = False
@@ -405,6 +414,34 @@ class EmbedEngine:
             self._ws[name] = t
         return t[:n].view(*shape)
 
+    @contextlib.contextmanager
+    def workspace(self, ws: Dict[str, torch.Tensor]):
+        """``with eng.workspace(ws) as ws:`` -- the body's buffers live in the dict ``ws``; the engine's own is back at the exit."""
+        keep, self._ws = self._ws, ws
+        try:
+            yield ws
+        finally:
+            self._ws = keep
+
+    # -- the named views of the workspace: shape and dtype of each in this one place
+    def rows_buf(self, nb: int) -> torch.Tensor:
+        return self._buf("slots0", (self.planes, nb * self.per0, 8), torch.int16)
+
+    def act_bufs(self, nb: int, last_planes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        return (self._buf("act1", (self.planes, nb * self.per1, 8), torch.int16),
+                self._buf("act2", (last_planes or self.planes, nb * self.per2, 8), torch.int16))
+
+    def dy_buf(self, li: int, nb: int, name: str = "dy") -> torch.Tensor:
+        cout, T, OH, OW = self.dims[li][1], *self.dims[li][5:8]
+        return self._buf("%s%d" % (name, li), (self.planes_bwd, nb * (cout // 8) * T * OH * OW, 8), torch.int16)
+
+    def scale_buf(self, name: str) -> torch.Tensor:
+        return self._buf(name, (4,), torch.float32)
+
+    def dx_buf(self, li: int, nb: int, name: str = "dx") -> torch.Tensor:
+        cin, _, t, h, w = self.dims[li][:5]
+        return self._buf("%s%d" % (name, li), (nb, t, h, w, cin), torch.float32)
+
     def set_weights(self, params: Sequence[torch.Tensor], quantize: Optional[str] = None, dither: int = 0,
                     quantize_levels: Sequence[int] = (0, 1, 2), slot: Optional[int] = None) -> None:
         """params = [w0, b0, w1, b1, w2, b2] fp32 on the device (ConvNet3D.features order).  ``quantize`` ('f16' /
@@ -462,8 +499,7 @@ class EmbedEngine:
         straight out of it through the index -- no per-step conversion of the real clips."""
         g = self.geo
         N = int(pool.shape[0])
-        rowp = P.pix_row_pitch(g.width)
-        per = g.frames * 3 * g.height * (rowp // 8)
+        per = self.per0
         rows = torch.empty((self.planes, N * per, 8), dtype=torch.int16, device=self.device)
         st = hip.stream_ptr(self.device)
         for i in range(0, N, step):
@@ -490,27 +526,23 @@ class EmbedEngine:
         feats = torch.empty((B, self.num_feat), dtype=torch.float32, device=self.device)
         saved = []
         st = hip.stream_ptr(self.device)
-        rowp = P.pix_row_pitch(g.width)
-        per1 = int(np.prod(self.fwd[0].plan.out_shape[:-1]))
-        per2 = int(np.prod(self.fwd[1].plan.out_shape[:-1]))
         for c0 in range(0, B, self.chunk):
             nb = min(self.chunk, B - c0)
-            n_slots0 = nb * g.frames * 3 * g.height * (rowp // 8)      # 16-byte units of the padded pixel rows
+            n_slots0 = nb * self.per0      # 16-byte units of the padded pixel rows
             cidx = None
             if rows is not None:      # batch = index into the resident, already converted pool
                 assert index is not None and rows.shape[0] == self.planes
                 slots0, n_slots0, cidx = rows, int(rows.shape[1]), index[c0:]
             else:
-                slots0 = self._buf("slots0", (self.planes, n_slots0, 8), torch.int16)
+                slots0 = self.rows_buf(nb)
                 lo = slots0[1] if self.planes == 2 else None
                 xin = x[c0:] if index is None else x
                 hip.run("vd_pix2rows", hip.ptr(xin), hip.ptr(None if index is None else index[c0:]), nb, g.frames, g.height,
                         g.width, hip.ptr(slots0[0]), hip.ptr(lo), self.prec, st)
-            n1, n2 = nb * per1, nb * per2
+            n1, n2 = nb * self.per1, nb * self.per2
             hilo = self.fwd2x is not None
             assert not (hilo and keep), "last_hilo engines have no kept-arg-max forward"
-            act1 = self._buf("act1", (self.planes, n1, 8), torch.int16)
-            act2 = self._buf("act2", (2 if hilo else self.planes, n2, 8), torch.int16)
+            act1, act2 = self.act_bufs(nb, 2 if hilo else None)
             am0 = am1 = am2 = None
             if keep:
                 am0 = torch.empty(n1 * 8, dtype=torch.uint8, device=self.device)
@@ -549,17 +581,13 @@ class EmbedEngine:
         per = B // G
         index = index.to(self.device, torch.int64).contiguous()
         feats = torch.empty((B, self.num_feat), dtype=torch.float32, device=self.device)
-        rowp = P.pix_row_pitch(g.width)
-        per1 = int(np.prod(self.fwd[0].plan.out_shape[:-1]))
-        per2 = int(np.prod(self.fwd[1].plan.out_shape[:-1]))
-        n1, n2 = B * per1, B * per2
+        per0, per1, per2 = self.per0, self.per1, self.per2
+        n_slots0, n1, n2 = B * per0, B * per1, B * per2
         hilo = self.fwd2x is not None
-        act1 = self._buf("act1", (1, n1, 8), torch.int16)
-        act2 = self._buf("act2", (2 if hilo else 1, n2, 8), torch.int16)
+        act1, act2 = self.act_bufs(B, 2 if hilo else None)
         w = self._weights
         if rows is None:
-            n_slots0 = B * g.frames * 3 * g.height * (rowp // 8)
-            slots0 = self._buf("slots0", (1, n_slots0, 8), torch.int16)
+            slots0 = self.rows_buf(B)
             hip.run("vd_pix2rows", hip.ptr(x.detach().to(torch.float32).contiguous()), hip.ptr(index), B, g.frames, g.height,
                     g.width, hip.ptr(slots0[0]), hip.ptr(None), self.prec, hip.stream_ptr(self.device))
         if self.fwd[0].breg_ok:       # register-resident-B kernel: reloads its fragments when a workgroup's walk crosses into the next set
@@ -573,7 +601,6 @@ class EmbedEngine:
                     self.fwd[0].run(rows, int(rows.shape[1]), w[1], act1.data_ptr() + s * per * per1 * 16, n1, None, per,
                                     clip_index=index[s * per:], group=s)
                 else:
-                    per0 = g.frames * 3 * g.height * (rowp // 8)
                     self.fwd[0].run(slots0[:, s * per * per0:], n_slots0, w[1], act1.data_ptr() + s * per * per1 * 16, n1, None, per, group=s)
         if getattr(self, "after_first_level", None) is not None:      # (distill.DMTrainer: an event behind the first level's launch)
             self.after_first_level()
@@ -601,35 +628,40 @@ class EmbedEngine:
         g_feat = g_feat.detach().to(torch.float32).contiguous()
         B = g_feat.shape[0]
         dx = torch.empty((B, g.frames, g.channel, g.height, g.width), dtype=torch.float32, device=self.device)
-        st = hip.stream_ptr(self.device)
         for c0, nb, am0, am1, am2 in saved:
             grad = g_feat[c0:c0 + nb]
             layout = 0
             for li, am in ((2, am2), (1, am1), (0, am0)):
-                cin, cout, t, h, w, T, OH, OW, To, Ho, Wo, pt = self.dims[li]
-                nslots = nb * (cout // 8) * T * OH * OW
-                dy = self._buf("dy%d" % li, (self.planes_bwd, nslots, 8), torch.int16)
-                lo = dy[1] if self.planes_bwd == 2 else None
-                sc = inv = None
-                if self.prec_bwd in (hip.PREC["f16"], hip.PREC["f16x3"]):
-                    # fp16 operands (also the hi/lo split ones): bring this layer's gradient into fp16's
-                    # exponent range with an exact power-of-two scale (DM gradients shrink by orders of
-                    # magnitude per layer and would otherwise fall into fp16's subnormals)
-                    scb = self._buf("gscale%d" % li, (4,), torch.float32)
-                    hip.run("vd_absmax_scale", hip.ptr(grad), grad.numel(), GRAD_TARGET(), hip.ptr(scb), st)
-                    sc, inv = scb, scb[1:]
-                hip.run("vd_unpool_relu_bwd", hip.ptr(grad), hip.ptr(am), nb, cout, To, Ho, Wo, pt, T, OH, OW, layout,
-                        hip.ptr(dy[0]), hip.ptr(lo), self.prec_bwd, hip.ptr(sc), st)
-                if lo is not None and os.environ.get("VD_BWD_X2_SIM") == "g":
-                    lo.zero_()      # measurement knob: the numerics of g_hi x (W_hi + W_lo)
-                if li == 0:
-                    out = dx[c0:c0 + nb]
-                else:
-                    out = self._buf("dx%d" % li, (nb, t, h, w, cin), torch.float32)
-                run_together(self.bwd[li], dy, nslots, None, out.data_ptr(), 0, None, nb, out_scale=inv)
-                grad = out
+                dy, nslots, _, inv = self.level_unpool(li, nb, grad, layout, am)
+                if self.planes_bwd == 2 and os.environ.get("VD_BWD_X2_SIM") == "g":
+                    dy[1].zero_()      # measurement knob: the numerics of g_hi x (W_hi + W_lo)
+                grad = dx[c0:c0 + nb] if li == 0 else self.dx_buf(li, nb)
+                self.level_dgrad(self.bwd[li], dy, nslots, grad, nb, inv)
                 layout = 1
         return dx
+
+    def level_unpool(self, li: int, nb: int, grad: torch.Tensor, layout: int, am, name: str = "dy", scale_name: str = "gscale", dense: bool = True):
+        """One level of a backward sweep up to its dense gradient: the pooled ``grad`` (``layout`` as vd_unpool_relu_bwd takes it) goes
+        through ReLU + max-pool backward into the slot buffer ``name`` (not when ``dense`` is off) -- fp16 operands, also the hi/lo split
+        ones, at an exact power-of-two scale measured into ``scale_name`` (DM gradients shrink by orders of magnitude per level and
+        would otherwise fall into fp16's subnormals).  -> (slots, slots per plane, scale, inverse scale); bf16 formats: no scales."""
+        st = hip.stream_ptr(self.device)
+        cout, T, OH, OW, To, Ho, Wo, pt = self.dims[li][1], *self.dims[li][5:12]
+        sc = inv = None
+        if self.prec_bwd in (hip.PREC["f16"], hip.PREC["f16x3"]):
+            sc = self.scale_buf("%s%d" % (scale_name, li))
+            hip.run("vd_absmax_scale", hip.ptr(grad), grad.numel(), GRAD_TARGET(), hip.ptr(sc), st)
+            inv = sc[1:]
+        slots = None
+        if dense:
+            slots = self.dy_buf(li, nb, name)
+            hip.run("vd_unpool_relu_bwd", hip.ptr(grad), hip.ptr(am), nb, cout, To, Ho, Wo, pt, T, OH, OW, layout,
+                    hip.ptr(slots[0]), hip.ptr(slots[1] if self.planes_bwd == 2 else None), self.prec_bwd, hip.ptr(sc), st)
+        return slots, nb * (cout // 8) * T * OH * OW, sc, inv
+
+    def level_dgrad(self, plans: Sequence[_DevPlan], slots: torch.Tensor, nslots: int, out: torch.Tensor, nb: int, inv) -> None:
+        """The input-gradient programs ``plans`` of a level from its dense gradient ``slots`` into ``out`` (fp32, x ``inv``)."""
+        run_together(plans, slots, nslots, None, out.data_ptr(), 0, None, nb, out_scale=inv)
 
 
 class WgradOp:

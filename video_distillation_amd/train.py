@@ -22,7 +22,7 @@ import torch
 from . import hip
 from . import plan as P
 from . import engine
-from .engine import EmbedEngine, WgradOp, _DevPlan, run_together, GRAD_TARGET
+from .engine import EmbedEngine, WgradOp, _DevPlan
 
 
 def standardize(x: torch.Tensor) -> torch.Tensor:
@@ -73,12 +73,16 @@ class TrainEngine:
             self._wg[(li, nb, det)] = op
         return op
 
-    def grads(self) -> List[torch.Tensor]:
+    def _split(self, flat: torch.Tensor, n_tensors: int = 8) -> List[torch.Tensor]:
+        """Views of a flat buffer as the first ``n_tensors`` parameter shapes."""
         out, o = [], 0
-        for s, n in zip(self.shapes, self.sizes):
-            out.append(self.gflat[o:o + n].view(*s))
+        for s, n in zip(self.shapes[:n_tensors], self.sizes[:n_tensors]):
+            out.append(flat[o:o + n].view(*s))
             o += n
         return out
+
+    def grads(self) -> List[torch.Tensor]:
+        return self._split(self.gflat)
 
     def _forward(self, x, params):
         """Forward with kept activations ("act1"/"act2" in the engine workspace) and arg-max bytes."""
@@ -88,12 +92,7 @@ class TrainEngine:
 
     # ------------------------------------------------------------------------------------
     def _acts(self, nb: int):
-        eng = self.eng
-        per1 = int(np.prod(eng.fwd[0].plan.out_shape[:-1]))
-        per2 = int(np.prod(eng.fwd[1].plan.out_shape[:-1]))
-        acts = [None, eng._buf("act1", (eng.planes, nb * per1, 8), torch.int16),
-                eng._buf("act2", (eng.planes, nb * per2, 8), torch.int16)]
-        return acts, [0, nb * per1, nb * per2]
+        return [None, *self.eng.act_bufs(nb)], [0, nb * self.eng.per1, nb * self.eng.per2]
 
     def head_forward(self, feats: torch.Tensor, mask: Optional[torch.Tensor], w: torch.Tensor, b: torch.Tensor) -> dict:
         """AvgPool3d -> dropout mask -> 1x1x1 conv -> max over frames (networks.py:741-745) of (B, num_feat) features.
@@ -133,32 +132,21 @@ class TrainEngine:
         engine's weights / packed dgrad operands must be current; activations are read from the engine workspace.
         ``keep_dense``: a second-order sweep will read the first layer's dense gradient slots (workspace ``dy0``); without
         it and without ``dx`` they are never materialised (``WgradOp.run_pooled``)."""
-        eng, st = self.eng, hip.stream_ptr(self.device)
+        eng = self.eng
         # (``acts_override`` = (activation views, plane strides): the clips are a slice of a larger forward, loss_and_grads_grouped)
         acts, act_plane = acts_override if acts_override is not None else self._acts(nb)
         grad, layout = g_feat, 0
-        scaled = eng.prec_bwd in (hip.PREC["f16"], hip.PREC["f16x3"])
         # ``side_wgrad``: the parameter side of a level (bias + weight gradient: staging, packing, one tile program, replica sum)
         # depends only on the level's incoming gradient, and nothing downstream depends on it -- it runs on a side stream under
         # the input-gradient passes of the same and the following levels; joined before returning
         main = torch.cuda.current_stream(self.device)
         side = self._side_stream() if (self.side_wgrad and g is not None) else None
         for li in (2, 1, 0):
-            cin, cout, t, h, w, T, OH, OW, To, Ho, Wo, pt = eng.dims[li]
-            nslots = nb * (cout // 8) * T * OH * OW
+            cout, To, Ho, Wo, pt = eng.dims[li][1], *eng.dims[li][8:12]
             dense = li > 0 or dx is not None or keep_dense   # the first layer's dense dy: pixel-gradient and second-order passes only
             if not dense and g is None:
                 break
-            sc = inv = None
-            if scaled:
-                scb = eng._buf("gscale%d" % li, (4,), torch.float32)
-                hip.run("vd_absmax_scale", hip.ptr(grad), grad.numel(), GRAD_TARGET(), hip.ptr(scb), st)
-                sc, inv = scb, scb[1:]
-            if dense:
-                dy = eng._buf("dy%d" % li, (eng.planes_bwd, nslots, 8), torch.int16)
-                lo = dy[1] if eng.planes_bwd == 2 else None
-                hip.run("vd_unpool_relu_bwd", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To, Ho, Wo, pt, T, OH, OW, layout,
-                        hip.ptr(dy[0]), hip.ptr(lo), eng.prec_bwd, hip.ptr(sc), st)
+            dy, nslots, sc, inv = eng.level_unpool(li, nb, grad, layout, am[li], dense=dense)
             if g is not None:
                 if side is not None:
                     side.wait_stream(main)          # the level's gradient and its scale are queued on the main stream
@@ -180,8 +168,8 @@ class TrainEngine:
                     else:
                         op.run_pooled(acts[li], False, act_plane[li], grad, am[li], layout, (To, Ho, Wo, pt), sc, g[2 * li], out_scale=inv)
             if li > 0 or dx is not None:
-                out = dx if li == 0 else eng._buf("dx%d" % li, (nb, t, h, w, cin), torch.float32)
-                run_together(eng.bwd[li], dy, nslots, None, out.data_ptr(), 0, None, nb, out_scale=inv)
+                out = dx if li == 0 else eng.dx_buf(li, nb)
+                eng.level_dgrad(eng.bwd[li], dy, nslots, out, nb, inv)
                 grad, layout = out, 1
         if side is not None:
             main.wait_stream(side)
@@ -191,14 +179,10 @@ class TrainEngine:
             self._side = torch.cuda.Stream(device=self.device)
         return self._side
 
-    def loss_and_grads(self, x: torch.Tensor, labels: torch.Tensor, params: Sequence[torch.Tensor],
-                       mask: Optional[torch.Tensor] = None, state: Optional[dict] = None):
-        """x (B,T,3,H,W) fp32 (already standardised), labels (B,) int64, params = the 8 network
-        tensors in ``parameters()`` order, mask (B,C,Tp) dropout multipliers or None.
-        Returns (mean CE loss [device scalar], logits (B,K), [8 gradient tensors]).  ``state`` (a dict)
-        receives what a second-order pass needs (GradMatchEngine)."""
-        eng, st = self.eng, hip.stream_ptr(self.device)
-        B = int(x.shape[0])
+    def _forward_head(self, x, labels, params, mask):
+        """What every loss starts with: operands packed, forward with kept activations, head forward, the per-clip loss and
+        logit-gradient buffers.  -> (x, labels [as the kernels read them], nb, arg-max bytes, head state, loss_c, dlog)."""
+        eng, B = self.eng, int(x.shape[0])
         x = x.detach().to(torch.float32).contiguous()
         labels = labels.to(self.device, torch.int64).contiguous()
         with engine.batched_packs():          # (forward + input-gradient operands of the three levels: one launch)
@@ -208,16 +192,24 @@ class TrainEngine:
                     dp.pack(eng._weights[2 * li])
         feats, nb, am = self._forward(x, params)
         hs = self.head_forward(feats, mask, params[6], params[7])
-        logits = hs["logits"]
-        loss_c = torch.empty(B, dtype=torch.float32, device=self.device)
-        dlog = torch.empty((B, self.K), dtype=torch.float32, device=self.device)
+        return (x, labels, nb, am, hs, torch.empty(B, dtype=torch.float32, device=self.device),
+                torch.empty((B, self.K), dtype=torch.float32, device=self.device))
+
+    def loss_and_grads(self, x: torch.Tensor, labels: torch.Tensor, params: Sequence[torch.Tensor],
+                       mask: Optional[torch.Tensor] = None, state: Optional[dict] = None):
+        """x (B,T,3,H,W) fp32 (already standardised), labels (B,) int64, params = the 8 network
+        tensors in ``parameters()`` order, mask (B,C,Tp) dropout multipliers or None.
+        Returns (mean CE loss [device scalar], logits (B,K), [8 gradient tensors]).  ``state`` (a dict)
+        receives what a second-order pass needs (GradMatchEngine)."""
+        x, labels, nb, am, hs, loss_c, dlog = self._forward_head(x, labels, params, mask)
+        B, logits, st = int(x.shape[0]), hs["logits"], hip.stream_ptr(self.device)
         hip.run("vd_ce_loss", hip.ptr(logits), hip.ptr(labels), B, self.K, hip.ptr(loss_c), hip.ptr(dlog), st)
         self.gflat.zero_()
         g = self.grads()
         g_feat = self.head_backward(hs, dlog, g[6], g[7])
         self.feat_backward(x, nb, am, g_feat, g, keep_dense=state is not None)
         if state is not None:
-            _, act_plane = self._acts(nb)
+            act_plane = [0, nb * self.eng.per1, nb * self.eng.per2]
             state.update(nb=nb, am=am, dropped=hs["dropped"], logits=logits, dlog=dlog, amt=hs["amt"], mask=hs["mask"],
                          wl=hs["wl"], act_plane=act_plane, x=x)
         return loss_c.mean(), logits, g
@@ -229,29 +221,18 @@ class TrainEngine:
         leaves a quarter of the chip idle in the last level and a tail in the others -- and one backward per sub-batch on its slice
         of the kept activations / arg-max bytes.  Returns (losses (groups,), logits, [8 gradients] per sub-batch); equal to
         per-sub-batch calls (tests/test_gpu_train.py::test_grouped_real_batches_equal_separate_calls)."""
-        eng, st = self.eng, hip.stream_ptr(self.device)
-        B = int(x.shape[0])
+        eng, st, B = self.eng, hip.stream_ptr(self.device), int(x.shape[0])
         if groups < 1 or B % groups != 0:
             raise ValueError("loss_and_grads_grouped: %d clips do not split into %d equal sub-batches" % (B, groups))
         per = B // groups
-        x = x.detach().to(torch.float32).contiguous()
-        labels = labels.to(self.device, torch.int64).contiguous()
-        with engine.batched_packs():          # (forward + input-gradient operands of the three levels: one launch)
-            eng.set_weights(params[:6])
-            for li in (1, 2):
-                for dp in eng.bwd[li]:
-                    dp.pack(eng._weights[2 * li])
-        feats, nb, am = self._forward(x, params)
-        hs = self.head_forward(feats, mask, params[6], params[7])
+        x, labels, nb, am, hs, loss_c, dlog = self._forward_head(x, labels, params, mask)
         logits = hs["logits"]
-        loss_c = torch.empty(B, dtype=torch.float32, device=self.device)
-        dlog = torch.empty((B, self.K), dtype=torch.float32, device=self.device)
         for k in range(groups):                 # (per sub-batch: vd_ce_loss scales the logit gradient by 1 / its batch size -- exactly what a
             sl = slice(k * per, (k + 1) * per)  #  separate call does; rescaling a 1 / B gradient would differ in the last bit, which the
             hip.run("vd_ce_loss", hip.ptr(logits[sl]), hip.ptr(labels[sl]), per, self.K, hip.ptr(loss_c[sl]),    # f16 passes' power-of-two
                     hip.ptr(dlog[sl]), st)                                                                       #  scaling can amplify)
         acts, act_plane = self._acts(nb)
-        per1, per2, nf = act_plane[1] // nb, act_plane[2] // nb, eng.num_feat
+        per1, per2, nf = eng.per1, eng.per2, eng.num_feat
         outs = []
         for k in range(groups):
             sl = slice(k * per, (k + 1) * per)
@@ -349,52 +330,36 @@ class GradMatchEngine(TrainEngine):
             return TrainEngine._forward(self, x, params)
         eng, ef, st = self.eng, self.eng_fwd, hip.stream_ptr(self.device)
         ef.set_weights(params[:6])
-        keep_ws, ef._ws = ef._ws, {}
-        try:
+        with ef.workspace({}):
             feats, saved = ef.forward(x, keep=True)
             (_, nb, am0, am1, am2), = saved
             g = self.geo
-            per1 = int(np.prod(eng.fwd[0].plan.out_shape[:-1]))
-            per2 = int(np.prod(eng.fwd[1].plan.out_shape[:-1]))
-            for name, n in (("act1", nb * per1), ("act2", nb * per2)):
-                src = ef._buf(name, (2, n, 8), torch.int16)
-                dst = eng._buf(name, (eng.planes, n, 8), torch.int16)
-                hip.run("vd_resplit_slots", hip.ptr(src[0]), hip.ptr(src[1]), n * 8, ef.prec, hip.ptr(dst[0]),
+            for src, dst in zip(ef.act_bufs(nb), eng.act_bufs(nb)):
+                hip.run("vd_resplit_slots", hip.ptr(src[0]), hip.ptr(src[1]), src[0].numel(), ef.prec, hip.ptr(dst[0]),
                         hip.ptr(dst[1] if eng.planes == 2 else None), eng.prec, st)
-            rowp = P.pix_row_pitch(g.width)
-            n_slots0 = nb * g.frames * 3 * g.height * (rowp // 8)
-            slots0 = eng._buf("slots0", (eng.planes, n_slots0, 8), torch.int16)
+            slots0 = eng.rows_buf(nb)
             hip.run("vd_pix2rows", hip.ptr(x), hip.ptr(None), nb, g.frames, g.height, g.width, hip.ptr(slots0[0]),
                     hip.ptr(slots0[1] if eng.planes == 2 else None), eng.prec, st)
-        finally:
-            ef._ws = keep_ws
         return feats, nb, (am0, am1, am2)
 
     def param_grads(self, x, labels, params, mask=None):
         """-> (loss, logits, [8 gradient tensors], state); state feeds ``vjp``."""
-        eng = self.eng
-        keep_ws, eng._ws = eng._ws, {}
         state = {}
-        try:
+        with self.eng.workspace({}) as state["ws"]:
             loss, logits, g = self.loss_and_grads(x, labels, params, mask, state=state)
             g = [t.clone() for t in g]
-        finally:
-            state["ws"], eng._ws = eng._ws, keep_ws
         return loss, logits, g, state
 
     # -- pieces of the adjoint sweep (shared by the fused ``vjp`` and the autograd path of ConvNet3D.forward) ----------
-    def _scale_buf(self, name: str) -> torch.Tensor:
-        return self.eng._buf(name, (4,), torch.float32)
-
     def _absmax_scale(self, t: torch.Tensor, name: str, target: float) -> torch.Tensor:
         """[2^k, 2^-k, scratch, -] on the device with max|t| * 2^k in [target / 2, target) (vd_absmax_scale)."""
-        scb = self._scale_buf(name)
+        scb = self.eng.scale_buf(name)
         hip.run("vd_absmax_scale", hip.ptr(t), t.numel(), target, hip.ptr(scb), hip.stream_ptr(self.device))
         return scb
 
     def _combine(self, a: torch.Tensor, b: Optional[torch.Tensor], mode: int, name: str) -> torch.Tensor:
         """mode 0: [a0 * b0, 1 / (a0 * b0)]; mode 1: [min(a0, b0), 1 / min] (device scalars, vd_scale_combine)."""
-        out = self._scale_buf(name)
+        out = self.eng.scale_buf(name)
         hip.run("vd_scale_combine", hip.ptr(a), hip.ptr(b), mode, hip.ptr(out), hip.stream_ptr(self.device))
         return out
 
@@ -425,18 +390,12 @@ class GradMatchEngine(TrainEngine):
                 self.sel[li].pack(torch.cat([V[2 * li], W[2 * li]], dim=1).contiguous())
 
     def _sweep_bufs(self, nb: int):
-        eng, geo = self.eng, self.geo
-        rowp = P.pix_row_pitch(geo.width)
-        n_slots0 = nb * geo.frames * 3 * geo.height * (rowp // 8)
-        per1 = int(np.prod(eng.fwd[0].plan.out_shape[:-1]))
-        per2 = int(np.prod(eng.fwd[1].plan.out_shape[:-1]))
-        n1, n2 = nb * per1, nb * per2
-        slots0 = eng._buf("slots0", (eng.planes, n_slots0, 8), torch.int16)
-        act1 = eng._buf("act1", (eng.planes, n1, 8), torch.int16)
-        act2 = eng._buf("act2", (eng.planes, n2, 8), torch.int16)
+        eng = self.eng
+        n1, n2 = nb * eng.per1, nb * eng.per2
+        slots0, (act1, act2) = eng.rows_buf(nb), eng.act_bufs(nb)
         gbar1 = eng._buf("gbar1", (eng.planes, n1, 8), torch.int16)
         gbar2 = eng._buf("gbar2", (eng.planes, n2, 8), torch.int16)
-        return n_slots0, n1, n2, slots0, act1, act2, gbar1, gbar2
+        return nb * eng.per0, n1, n2, slots0, act1, act2, gbar1, gbar2
 
     def _up_sweep(self, nb: int, am, V: Sequence[torch.Tensor], W: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
         """gbar_{l+1} = P_l (conv(a_l, V_l) + vb_l + conv(gbar_l, W_l)), gbar_0 = 0  ->  gbar_3 (nb, num_feat): the tangent
@@ -478,26 +437,20 @@ class GradMatchEngine(TrainEngine):
         dx = torch.empty((nb, geo.frames, geo.channel, geo.height, geo.width), dtype=torch.float32, device=self.device)
         grad, layout = abar, 0
         for li in (2, 1, 0):
-            cin, cout, t, h, w, T, OH, OW, To, Ho, Wo, pt = eng.dims[li]
-            nslots = nb * (cout // 8) * T * OH * OW
-            dy = eng._buf("dy%d" % li, (eng.planes_bwd, nslots, 8), torch.int16)       # dz_l of the first-order pass
-            zb = eng._buf("zb%d" % li, (eng.planes_bwd, nslots, 8), torch.int16)
-            lo = zb[1] if eng.planes_bwd == 2 else None
-            sz = inv_z = inv_dv = inv_gd = None
+            cout, To, Ho, Wo = eng.dims[li][1], *eng.dims[li][8:11]
+            dy = eng.dy_buf(li, nb)       # dz_l of the first-order pass
+            inv_dv = inv_gd = None
             if self.scaled:
-                # zb_l = P_l^T abar_{l+1} at its own scale; dy_l carries the first-order pass's scale of this level (gscale%d of
-                # TrainEngine.feat_backward, kept in the step's workspace), V_l and gbar_l the scales of the upward sweep
-                sz = self._absmax_scale(grad, "zscale%d" % li, GRAD_TARGET())
-                inv_z = sz[1:]
-                gs = self._scale_buf("gscale%d" % li)
+                # dy_l carries the first-order pass's scale of this level (gscale%d of TrainEngine.feat_backward, kept in the
+                # step's workspace), V_l and gbar_l the scales of the upward sweep; zb_l = P_l^T abar_{l+1} gets its own (zscale%d)
+                gs = eng.scale_buf("gscale%d" % li)
                 inv_dv = self._combine(gs, self._sv[li], 0, "dvscale%d" % li)[1:]
                 if hv and li > 0:
                     inv_gd = self._combine(gs, self._sg[li], 0, "gdscale%d" % li)[1:]
-            hip.run("vd_unpool_relu_bwd", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To, Ho, Wo, pt, T, OH, OW, layout,
-                    hip.ptr(zb[0]), hip.ptr(lo), eng.prec_bwd, hip.ptr(sz), st)
-            out = dx if li == 0 else eng._buf("ax%d" % li, (nb, t, h, w, cin), torch.float32)
-            run_together(eng.bwd[li], zb, nslots, None, out.data_ptr(), 0, None, nb, out_scale=inv_z)
-            run_together(self.bwdV[li], dy, nslots, None, out.data_ptr(), 0, None, nb, out_scale=inv_dv)   # (accumulates on top of the stores above)
+            zb, nslots, _, inv_z = eng.level_unpool(li, nb, grad, layout, am[li], name="zb", scale_name="zscale")
+            out = dx if li == 0 else eng.dx_buf(li, nb, "ax")
+            eng.level_dgrad(eng.bwd[li], zb, nslots, out, nb, inv_z)
+            eng.level_dgrad(self.bwdV[li], dy, nslots, out, nb, inv_dv)   # (accumulates on top of the stores above)
             if hv:
                 # parameter side: z_l = conv(a_l, W_l) + b_l carries zbar_l, and g_{a_l} = convT(dz_l, W_l) carries gbar_l
                 op = self._wgrad(li, nb)
@@ -513,12 +466,7 @@ class GradMatchEngine(TrainEngine):
         return dx
 
     def _views(self, n_tensors: int):
-        flat = torch.zeros(sum(self.sizes[:n_tensors]), dtype=torch.float32, device=self.device)
-        out, o = [], 0
-        for shp, n in zip(self.shapes[:n_tensors], self.sizes[:n_tensors]):
-            out.append(flat[o:o + n].view(*shp))
-            o += n
-        return out
+        return self._split(torch.zeros(sum(self.sizes[:n_tensors]), dtype=torch.float32, device=self.device), n_tensors)
 
     def head_second_order(self, hs: dict, dlog: torch.Tensor, gbar_feat: torch.Tensor, v_w: torch.Tensor, v_b: torch.Tensor,
                           want_params: bool, hessian: bool):
@@ -543,13 +491,11 @@ class GradMatchEngine(TrainEngine):
         """d (sum_i <v_i, g_i(x)>) / dx for the ``param_grads`` call that produced ``state``.  With
         ``param_adjoint`` also d (sum_i <v_i, g_i>) / d params -- the Hessian-vector product H v of the
         CE loss w.r.t. the parameters (MTT's unrolled inner loop) -- returned as (dx, [8 tensors])."""
-        eng = self.eng
         nb, am = state["nb"], state["am"]
         W = [p.detach().to(self.device, torch.float32).contiguous() for p in params]
         V = [torch.zeros_like(w) if t is None else t.detach().to(self.device, torch.float32).contiguous().view_as(w)
              for t, w in zip(v, W)]
-        keep_ws, eng._ws = eng._ws, state["ws"]
-        try:
+        with self.eng.workspace(state["ws"]):
             self._pack_adjoint(W, V)
             hv = self._views(8) if param_adjoint else None
             gbar3 = self._up_sweep(nb, am, V, W)
@@ -559,8 +505,6 @@ class GradMatchEngine(TrainEngine):
                 hv[6].view(self.K, self.C).copy_(wbar)
                 hv[7].copy_(bbar)
             dx = self._down_sweep(nb, am, abar, state["x"], hv)
-        finally:
-            eng._ws = keep_ws
         return (dx, hv) if param_adjoint else dx
 
     # -- autograd path: every piece as its own call with caller-held state (networks._FeatFunction / _HeadFunction) --------
@@ -570,14 +514,10 @@ class GradMatchEngine(TrainEngine):
         """features (B, num_feat) of the clips with the activations / arg-max of all levels kept -> (feats, fstate)."""
         eng = self.eng
         x = x.detach().to(self.device, torch.float32).contiguous()
-        keep_ws, eng._ws = eng._ws, {}
-        try:
+        with eng.workspace({}) as ws:
             if self.scaled:      # (the fused entry, loss_and_grads, packs the engine's forward operands itself)
                 eng.set_weights([p.detach() for p in params6])
             feats, nb, am = self._forward(x, [p.detach() for p in params6])
-            ws = eng._ws
-        finally:
-            eng._ws = keep_ws
         return feats, dict(ws=ws, nb=nb, am=am, x=x)
 
     def ag_feat_backward(self, fs: dict, g_feat: torch.Tensor, params6: Sequence[torch.Tensor], need_dx: bool,
@@ -589,8 +529,7 @@ class GradMatchEngine(TrainEngine):
         if not keep:
             ws.update(getattr(self, "_scratch", {}))
         W = [p.detach().to(self.device, torch.float32).contiguous() for p in params6]
-        keep_ws, eng._ws = eng._ws, ws
-        try:
+        with eng.workspace(ws):
             with engine.batched_packs():
                 for li in ((0, 1, 2) if need_dx else (1, 2)):
                     for dp in eng.bwd[li]:
@@ -600,8 +539,6 @@ class GradMatchEngine(TrainEngine):
             dx = torch.empty((fs["nb"], geo.frames, geo.channel, geo.height, geo.width), dtype=torch.float32,
                              device=self.device) if need_dx else None
             self.feat_backward(fs["x"], fs["nb"], fs["am"], g_feat.detach().to(torch.float32).contiguous(), g, dx, keep_dense=keep)
-        finally:
-            eng._ws = keep_ws
         if not keep:
             self._scratch = {k: v for k, v in ws.items() if k not in self._KEEP}
             return dx, g, None
@@ -616,13 +553,10 @@ class GradMatchEngine(TrainEngine):
         W = [p.detach().to(self.device, torch.float32).contiguous() for p in params6]
         V = [torch.zeros_like(w) if t is None else t.detach().to(self.device, torch.float32).contiguous().view_as(w)
              for t, w in zip(v6, W)]
-        keep_ws, eng._ws = eng._ws, bs["ws"]
-        try:
+        with eng.workspace(bs["ws"]):
             self._pack_adjoint(W, V)
             hv = self._views(6) if need_params else None
             gbar3 = self._up_sweep(nb, am, V, W)
             abar = torch.zeros((nb, eng.num_feat), dtype=torch.float32, device=self.device)
             xbar = self._down_sweep(nb, am, abar, fs["x"], hv)
-        finally:
-            eng._ws = keep_ws
         return gbar3, xbar, hv
