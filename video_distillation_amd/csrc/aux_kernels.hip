@@ -1174,8 +1174,7 @@ extern "C" int vd_hallucinator_bwd(const float* g_out, const float* stat, const 
     const int tiles_x = (W + HAL_TW - 1) / HAL_TW, tiles_y = (H + HAL_TH - 1) / HAL_TH;
     if (fused && (g_w != nullptr) == (g_b != nullptr) && (fused >= 2 || (int64_t)n * tiles_x * tiles_y >= 1024)) {
         int64_t grid = (int64_t)n * tiles_x * tiles_y;
-        static const int cap = getenv("VD_HAL_GRID") ? atoi(getenv("VD_HAL_GRID")) : 512;
-        if (grid > cap) grid = cap;
+        if (grid > 512) grid = 512;
         hipLaunchKernelGGL(hal_bwd_fused_kernel, dim3((unsigned)grid), dim3(256), 0, st, g_out, stat, dyn, sidx, didx, w, n, T, H, W,
                            tiles_x, tiles_y, g_dyn, g_stat, g_w, g_b);
         return (int)hipGetLastError();
@@ -1188,8 +1187,7 @@ extern "C" int vd_hallucinator_bwd(const float* g_out, const float* stat, const 
         int64_t chunks = (total + 255) / 256;
         // (256 blocks per job: more blocks cost more in the closing atomics -- every block adds onto the same <= 81 addresses --
         //  than they gain in parallelism: 0.17 ms at 256, 0.25 at 1024, 0.43 at 2560 for 50 clips 112x112x16)
-        static const int cap = getenv("VD_HAL_CHUNKS") ? atoi(getenv("VD_HAL_CHUNKS")) : 256;
-        if (chunks > cap) chunks = cap;
+        if (chunks > 256) chunks = 256;
         hipLaunchKernelGGL(hal_bwd_param_kernel, dim3((unsigned)chunks, 6), dim3(256), 0, st, g_out, stat, dyn, sidx,
                            didx, n, T, H, W, g_w, g_b);
         e = (int)hipGetLastError();

@@ -32,25 +32,12 @@
 
 #include "../../include/vd_hip.h"
 
-// tuning switches (compile-time A/B builds; defaults are the shipped configuration)
-#ifndef VD_DB_X1
-#define VD_DB_X1 3
-#endif
-#ifdef VD_NO_SCHED_BARRIER
-#define VD_SCHED_BARRIER()
-#else
+// scheduling helpers of the K loops (each was a compile-time A/B switch; what is left is the measured winner)
 #define VD_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#endif
-#ifndef VD_NO_SETPRIO_LOOP      // (round 5: the single-pass K loop of a channel chunk runs at priority 2 -- above a partner workgroup's patch DMA /
-#define VD_PRIO_LOOP(x) __builtin_amdgcn_s_setprio(x)      //  epilogue phases on the same SIMD: level 1 -0.8 % alone, the DM step -0.1 ms in
-#else                           //  four of four same-box pairs, profiles/r05_prioloop_ab.txt)
-#define VD_PRIO_LOOP(x)
-#endif
-#ifdef VD_SETPRIO
-#define VD_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define VD_PRIO(x)
-#endif
+// (round 5: the single-pass K loop of a channel chunk runs at priority 2 -- above a partner workgroup's patch DMA /
+//  epilogue phases on the same SIMD: level 1 -0.8 % alone, the DM step -0.1 ms in
+//  four of four same-box pairs, profiles/r05_prioloop_ab.txt)
+#define VD_PRIO_LOOP(x) __builtin_amdgcn_s_setprio(x)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -163,9 +150,6 @@ __device__ __forceinline__ void split16(float v, uint16_t& hi, uint16_t& lo) {
 #else
 #define VD_DBG(p) 0
 #endif
-#ifndef VD_OCC_SMALL
-#define VD_OCC_SMALL 2
-#endif
 // SQ (hi+lo formats): PLANE-SEQUENTIAL K loop -- only ONE operand plane of a channel chunk's patch is resident at a time: the chunk
 // runs as two passes, (A_hi x B_lo + A_hi x B_hi) over the high plane, then A_lo x B_hi over the low plane staged into the same
 // LDS, so the program needs the LDS of a single-pass one and TWO workgroups share a CU where one did.  Same products; the
@@ -173,8 +157,9 @@ __device__ __forceinline__ void split16(float v, uint16_t& hi, uint16_t& lo) {
 // It pays where a box has ONE chunk and a patch that is expensive to stage -- the first level (2 x 55 KB of dword-aligned kw-slots
 // per box: 5.44 -> 4.81 ms per 512 clips, same box) -- and costs where the chunks are many and short (16 chunks of the last
 // level: twice the chunk boundaries, 0.66 -> 0.77 ms; level 1: 8.29 -> 8.40), so only the first-level programs are dispatched to it.
-#define VD_OCC(PREC, MTW, NTW, BAL) \
-    ((((MTW) * (NTW) + (BAL)) <= 4 && ((PREC) == VD_PREC_BF16 || (PREC) == VD_PREC_F16)) ? VD_OCC_SMALL : 2)
+// waves per SIMD of every instantiation (three for the small single-pass ones -- <= 4 accumulator tiles per wave -- spilled 60
+// registers to scratch under the 168-register cap: 2.34 -> 3.2 ms, docs/history.md)
+#define VD_OCC(PREC, MTW, NTW, BAL) 2
 // NTW = N tiles (of 32 output channels) per wave: with 2, an A fragment read from LDS feeds two MFMAs,
 // which halves the LDS read traffic per MFMA (the co-critical resource of the NTW = 1 layout).
 // BAL = 1 (with NTW = 2, MTW = 3): boxes of 7 M tiles on 2 x 2 waves -- every wave owns 3 M tiles x 2 N
@@ -209,7 +194,7 @@ __device__ __forceinline__ void conv_mfma_body(const VdConvParams& p, const int 
     constexpr int H0 = (MTW + 1) / 2;   // tiles whose A fragments are fetched one half-step ahead
     constexpr int H1 = MTW - H0;
     constexpr int AD = 1;                               // x1: A-fragment prefetch distance (K-steps)
-    constexpr int DB = C8 ? 3 : X3 ? (TILES <= 2 ? 5 : ((SEQ && NTW == 1) ? 3 : 2)) : VD_DB_X1;     // (C8: a ring of 4 = one correction group)   // B-fragment prefetch distance (K steps); x1: (DB+1) % (AD+1) == 0
+    constexpr int DB = C8 ? 3 : X3 ? (TILES <= 2 ? 5 : ((SEQ && NTW == 1) ? 3 : 2)) : 3;     // (C8: a ring of 4 = one correction group)   // B-fragment prefetch distance (K steps); x1: (DB+1) % (AD+1) == 0
     //   (plane-sequential: the low-plane pass has one MFMA per tile and step instead of three, so its steps are short)
     static_assert(X3 || (DB + 1) % (AD + 1) == 0, "ring sizes must divide the unroll factor");
     constexpr int LU = C8 ? 6 : (TILES <= 4) ? 14 : 17;   // DMA groups per wave whose gather entries stay in registers (4 waves x LU x 64 slots >= the plan's patch;
@@ -311,10 +296,7 @@ __device__ __forceinline__ void conv_mfma_body(const VdConvParams& p, const int 
     //     so they are requested first; they are the same for every channel chunk and stay in registers.
     const int32_t* gtab = p.gather + (int64_t)bi * p.gather_stride;
     constexpr bool HOIST = (TILES < 8);   // MTW = 8 has no registers to spare: it re-reads the table per chunk
-#ifndef VD_C8_HOIST
-#define VD_C8_HOIST 1
-#endif
-    const bool hoist = HOIST && (!C8 || (VD_C8_HOIST && ngroups <= nwaves * LU));
+    const bool hoist = HOIST && (!C8 || ngroups <= nwaves * LU);
     uint32_t goff[HOIST ? LU : 1];
 #pragma unroll
     for (int u = 0; u < (HOIST ? LU : 1); ++u) {
@@ -491,12 +473,11 @@ __device__ __forceinline__ void conv_mfma_body(const VdConvParams& p, const int 
                 for (int i = 0; i < MA; ++i) A[d][i] = *reinterpret_cast<const uint4*>(smem + a_off[i] + tp);
             }
             int tp = tap_of(AD + 1);          // tap offset of step s + 2
-            VD_PRIO_LOOP(2);                  // (A/B switch: the whole K loop of a chunk above a partner workgroup's DMA / epilogue phases)
+            VD_PRIO_LOOP(2);                  // (the whole K loop of a chunk above a partner workgroup's DMA / epilogue phases)
             auto k_step = [&](const int u, const int s_abs) {
                 load_b(s_abs + DB, bqh[(u + DB) % (DB + 1)], bql[(u + DB) % (DB + 1)]);
                 const int tp_next = tap_of(s_abs + AD + 2);
                 VD_SCHED_BARRIER();
-                VD_PRIO(1);
 #pragma unroll
                 for (int i = 0; i < MTW; ++i) {
                     if (NTW == 2 && BAL == 0 && i == MTW - 1 && short_row) continue;
@@ -515,7 +496,6 @@ __device__ __forceinline__ void conv_mfma_body(const VdConvParams& p, const int 
                     VD_SCHED_BARRIER();
                     A[u % (AD + 1)][MTW] = *reinterpret_cast<const uint4*>(smem + a_off[MTW] + tp);
                 }
-                VD_PRIO(0);
                 VD_SCHED_BARRIER();
                 tp = tp_next;
             };
@@ -1123,18 +1103,15 @@ __global__ __launch_bounds__(256, VD_OCC(PREC, MTW, NTW, BAL)) void conv_mfma_mu
     conv_mfma_body<PREC, MTW, SO, NTW, BAL>(m.p[k], 1, m.total[k], b - m.first[k], m.first[k + 1] - m.first[k]);
 }
 
-// tuning switches of the first-level kernel (A/B builds: tools/l0_variants.sh)
-#ifndef VD_L0_D
-#define VD_L0_D 6          // A fragments in flight in the frame-sharing K loop
-#endif
-#ifndef VD_L0_PRIO
-#define VD_L0_PRIO 1       // s_setprio 3 around the K loop: the partner wave on the SIMD is in its vector-ALU phase (same box: 8.53 -> 8.33 ms)
-#endif
+// tuning of the first-level kernel (the winners of round 5's A/B builds): 6 A fragments in flight in the frame-sharing K loop (D below),
+// s_setprio 3 around that K loop (the partner wave on the SIMD is in its vector-ALU phase; same box: 8.53 -> 8.33 ms)
 #ifndef VD_L0_TOUCH
 #define VD_L0_TOUCH 0      // 1: touch the next box's rows from inside the K loop (one dword per row half into a register nobody reads, so that
                            // the next phase's row loads hit the caches).  Measured SLOWER on the same box, 8.53 vs 7.90 ms per 3200 clips
                            // (profiles/r05_l0_variants.txt): with the box scalars prefetched and the stores moved behind the expansion the
-                           // other phase is the shorter one, and everything added to the K phase lengthens the critical one
+                           // other phase is the shorter one, and everything added to the K phase lengthens the critical one.
+                           // (The last compile-time switch left: the K-loop lambda captures touch_rows even with the statement discarded,
+                           // and without that capture the compiler allocates the registers of conv0_breg_kernel<., true> differently)
 #endif
 #define VD_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")      // (no vmcnt wait: global loads stay in flight)
 
@@ -1378,7 +1355,7 @@ __global__ __launch_bounds__(512, 1) void conv0_breg_kernel(const VdConvParams p
                     // q = 7 c + kh: pair j holds q = 2 j (lanes 0-31) and 2 j + 1 (lanes 32-63) -- 144 bytes apart (pa), except
                     // q = 6 / 7 which straddle two channels (pb); left-over taps: q = 20 of kt = 0 / 1 (step 30), of kt = 2 and the
                     // zero tap (step 31: the upper lanes read the lower lanes' address, their B operand is zero)
-                    constexpr int D = VD_L0_D, NR = 68;
+                    constexpr int D = 6, NR = 68;
                     constexpr int FSTRIDE = 3 * PF * 16;
                     uint4 R[D];
                     const char* pa = patch + a_off[0] + half * (PH * 16);
@@ -1397,7 +1374,7 @@ __global__ __launch_bounds__(512, 1) void conv0_breg_kernel(const VdConvParams p
                         }
                     };
                     vd_static_for<D>([&](auto rc) { R[decltype(rc)::v] = rd(rc); });
-                    if (VD_L0_PRIO) __builtin_amdgcn_s_setprio(3);      // (the partner wave on this SIMD is in its vector-ALU phase)
+                    __builtin_amdgcn_s_setprio(3);      // (the partner wave on this SIMD is in its vector-ALU phase)
                     vd_static_for<NR>([&](auto rc) {
                         constexpr int r = decltype(rc)::v;
                         if constexpr (r < 60) {
@@ -1423,7 +1400,7 @@ __global__ __launch_bounds__(512, 1) void conv0_breg_kernel(const VdConvParams p
                         // those waits must not see the touch loads
                         if constexpr (r == 5 && VD_L0_TOUCH) { touch_rows(); __builtin_amdgcn_sched_barrier(0); }
                     });
-                    if (VD_L0_PRIO) __builtin_amdgcn_s_setprio(0);
+                    __builtin_amdgcn_s_setprio(0);
                 } else {
                     uint4 A[2][MTW];
                     const int tp0 = lds_tap[half], tp1 = lds_tap[2 + half];
@@ -1588,11 +1565,6 @@ static int launch(const VdConvParams& p, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-static bool vd_first_level_seq_enabled() {       // VD_X3_SEQ=0: both planes resident everywhere (A/B measurements)
-    static const bool on = [] { const char* e = getenv("VD_X3_SEQ"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 extern "C" int vd_conv_mfma(const VdConvParams* pp, void* stream) {
     if (pp == nullptr) return -1;
     const VdConvParams& p = *pp;
@@ -1661,7 +1633,7 @@ extern "C" int vd_conv_mfma(const VdConvParams* pp, void* stream) {
     //  bytes -- in that plane: a program whose plane is smaller than its staging falls through to the two-plane kernel)
     const int64_t sq_stage = (p.epi == VD_EPI_POOL_CL && p.argmax == nullptr)
         ? (int64_t)2 * p.MW * p.MTW * 4 * (p.pool_t == 2 ? 1 : 2) * p.NT * 32 * 2 : 0;
-    if (p.MTW == 4 && p.CC == 1 && p.ncl == 1 && sq_stage <= p.lds_plane_bytes && vd_first_level_seq_enabled()) {
+    if (p.MTW == 4 && p.CC == 1 && p.ncl == 1 && sq_stage <= p.lds_plane_bytes) {
         if (p.prec == VD_PREC_BF16X3) return launch<VD_PREC_BF16X3, 4, false, 1, 0, true>(p, st);
         if (p.prec == VD_PREC_F16X3) return launch<VD_PREC_F16X3, 4, false, 1, 0, true>(p, st);
     }

@@ -667,8 +667,7 @@ void layer_input(int layer, int frames, int height, int width, int& cin, int& t,
 // a TINY launch, fewer workgroups than a quarter of the chip's 512 slots -- fewer M tiles per wave whatever it pads
 bool latency_better(const Plan& alt, const Plan& best, const Plan& base, int batch_hint) {
     if (alt.grid(batch_hint) <= best.grid(batch_hint)) return false;
-    const char* e = getenv("VD_TINY_GRID");
-    const int tiny_grid = e != nullptr ? atoi(e) : 128;
+    const int tiny_grid = 128;      // plan.TINY_GRID
     const bool tiny = best.grid(batch_hint) < tiny_grid && alt.MTW < best.MTW && alt.grid(batch_hint) <= 512;
     return (double)alt.rows_total <= (double)base.rows_total * 1.05 || tiny;
 }

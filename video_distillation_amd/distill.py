@@ -156,6 +156,7 @@ class _NullCtx:
 
 class HipBackend:
     """Production backend: EmbedEngine (MFMA kernels) + the small HIP kernels."""
+    PREP_MIN_CLIPS = 1600      # real clips per step from which the operand packing moves to its own stream (prepare_real_weights)
 
     def __init__(self, geo: P.NetGeometry, device, prec_real: str = "f16", prec_syn: str = "f16x3", chunk: int = 512,
                  prec_bwd: Optional[str] = "f16x3", syn_batch_hint: Optional[int] = None, real_last: Optional[str] = None):
@@ -195,9 +196,8 @@ class HipBackend:
         # across iterations: the backward of step i runs under the real forward of step i+1.
         self.two_streams = (self.eng_syn is not self.eng_real)
         if self.two_streams:
-            pr, ps = (int(v) for v in os.environ.get("VD_STREAM_PRIO", "0,-1").split(","))
-            self.s_real = torch.cuda.Stream(device=self.device, priority=pr)
-            self.s_syn = torch.cuda.Stream(device=self.device, priority=ps)
+            self.s_real = torch.cuda.Stream(device=self.device, priority=0)
+            self.s_syn = torch.cuda.Stream(device=self.device, priority=-1)
         self._ev_real = None
         self.s_prep = None                 # preparation stream (prepare_real_weights), created on first use
         self._real_done: Dict[int, "torch.cuda.Event"] = {}      # per buffer set: behind the launches that last read it
@@ -210,8 +210,7 @@ class HipBackend:
         # reference's (gradient off by 3e-2).  So the synthetic clips get TWO forwards: one with the exact weights,
         # whose ReLU / arg-max decisions route the gradient exactly as the reference does, and a "value pass" with
         # rn16(W), whose features enter the loss -- both sides of the difference then carry the same perturbation.
-        self.weight_format = prec_real if (prec_real in ("f16", "bf16") and prec_syn == prec_real + "x3"
-                                           and os.environ.get("VD_VALUE_PASS", "1") == "1") else None
+        self.weight_format = prec_real if (prec_real in ("f16", "bf16") and prec_syn == prec_real + "x3") else None
         # The better remedy where the real batch of a class has >= 4 clips: DITHER the real side's weights instead.  The
         # class's clips are dealt to G launch groups; group g multiplies by weights rounded down / up such that every
         # weight's mean over the groups is the fp32 value to 1/(2G) ulp (vd_pack_weights_dither), so the perturbation of
@@ -220,7 +219,7 @@ class HipBackend:
         self.prec_real = prec_real
         self.dither_enabled = True      # (tests switch it off per backend to measure the other two remedies)
         self._dither = 0
-        self.resident_rows = os.environ.get("VD_RESIDENT_ROWS", "1") == "1"
+        self.resident_rows = True      # (tests switch it off per backend: the per-step conversion of the real clips)
         self._pool_rows = None
 
     def new_network(self, seed: int):
@@ -261,7 +260,7 @@ class HipBackend:
         # (only where the real side is long: with the 400 clips per rank of an 8-rank job the step is 5 ms and issue-bound -- there the
         #  extra stream's events cost up to 0.5 ms of it, `profiles/r04_rank_proxy_knobs.txt` -- so ``nclips`` below 1600 packs in line)
         if not self.two_streams or os.environ.get("VD_PREP_STREAM", "1") != "1" or \
-                (nclips is not None and nclips < int(os.environ.get("VD_PREP_MIN_CLIPS", "1600"))):
+                (nclips is not None and nclips < self.PREP_MIN_CLIPS):
             self._prep_slot = None
             return self.set_real_weights(weights, per_class)
         if self.s_prep is None:
@@ -1189,7 +1188,7 @@ class GMTrainer:
         """All class terms on the caller's stream; with a HIP backend the real batch of class k+1 is prefetched on a side
         stream under the synthetic-clip passes of class k."""
         total = torch.zeros((), device=dev)
-        overlap = hasattr(ops, "param_grads_async") and os.environ.get("VD_GM_OVERLAP", "1") == "1"
+        overlap = hasattr(ops, "param_grads_async")
 
         def real_side(k):
             c = self.classes[k]

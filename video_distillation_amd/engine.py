@@ -54,7 +54,7 @@ class _DevPlan:
         p.src_clip_stride4, p.src_chunk_stride4 = plan.clip_stride4, plan.chunk_stride4
         p.NT, p.MW, p.MTW, p.NTW = plan.NT, plan.MW, plan.MTW, plan.NTW
         mt_max = max(t.mt for t in plan.types)
-        p.mt_valid = mt_max if (plan.NTW == 2 and mt_max < plan.MW * plan.MTW and os.environ.get("VD_SKIP_PAD", "1") == "1") else 0
+        p.mt_valid = mt_max if (plan.NTW == 2 and mt_max < plan.MW * plan.MTW) else 0
         p.epi, p.pool_t, p.relu = plan.epi, plan.pool_t, int(plan.relu)
         p.n_out, p.n_stride = plan.n_out, plan.n_stride
         p.out_clip_stride = plan.out_clip_stride
@@ -62,7 +62,7 @@ class _DevPlan:
         p.pair_flip = plan.pair_flip
         p.lds_plane_bytes = int(gt.shape[1]) * 16
         p.ntypes = len(plan.types)
-        p.persist = int(os.environ.get("VD_PERSIST", str(P.BOX_WALK_GENERATIONS)))
+        p.persist = P.BOX_WALK_GENERATIONS
         if os.environ.get("VD_NO_ALT") == "1":       # A/B: hi+lo programs without the per-chunk sign alternation of their accumulation (conv_mfma.hip ALT)
             p.persist |= 0x100000
         p.tab_ofs[0], p.tab_ofs[1], p.tab_ofs[2] = int(desc[0][7]), int(desc[0][8]), int(desc[0][9])
@@ -139,7 +139,7 @@ class _DevPlan:
         p = self.params
         p.emit_lo = int(emit_lo)        # single-pass program, staged pooled epilogue: 1 = also write the fp16 low plane (dst_plane_stride
         #                                 behind), 2 = write fp8 low parts there instead (for a VD_PREC_F16C8 consumer)
-        if int(emit_lo) == 2 and _RANGE_MONITOR:      # ... whose fixed scalings hold for a RANGE of output magnitudes: the launch records what it saw
+        if int(emit_lo) == 2:      # ... whose fixed scalings hold for a RANGE of output magnitudes: the launch records what it saw
             if self.range_stats is None:
                 self.range_stats = torch.zeros(2, dtype=torch.int32, device=src.device)
             p.range_stats = self.range_stats.data_ptr()
@@ -187,9 +187,6 @@ def GRAD_TARGET() -> float:
     """max |g| * scale of a gradient operand lies in [target / 2, target) (vd_absmax_scale) before its 16-bit split: fp16's largest
     number is 65504, an fp16 PAIR carries 22 bits for elements down to 2^-2, i.e. 2^-12 of the largest at 1024 (VD_GRAD_TARGET: A/B)."""
     return float(os.environ.get("VD_GRAD_TARGET", "1024"))
-
-
-_RANGE_MONITOR = os.environ.get("VD_RANGE_MONITOR", "1") == "1"      # (0: A/B of the monitor's cost in the level-1 epilogue)
 
 
 class _PackState(threading.local):       # per host thread: packs queued by one thread are flushed on that thread's current stream
@@ -335,14 +332,13 @@ class EmbedEngine:
         self.chunk = int(chunk)
         # two N tiles per wave (half the LDS reads per MFMA): layer-1/2 forward programs whose boxes fill 8 M
         # tiles, and the first layer in the single-pass formats (measured: x1 +7 %, x3 -6 % -> x3 keeps one)
-        self.ntw = int(os.environ.get("VD_NTW", "2"))
         if ntw0 is None:
             # (x1 formats: the register-resident-B kernel runs the 2x2-wave one-N-tile layout)
             breg = os.environ.get("VD_L0_BREG", "5") in ("4", "5")
-            ntw0 = int(os.environ.get("VD_NTW0", "1" if (hip.is_x3(self.prec) or self.ntw != 2 or breg) else "2"))
-        bal = (self.ntw == 2 and not hip.is_x3(self.prec) and os.environ.get("VD_BALANCED", "1") == "1")
+            ntw0 = 1 if (hip.is_x3(self.prec) or breg) else 2
+        bal = not hip.is_x3(self.prec)
         self.batch_hint = batch_hint      # typical clips per launch: small batches get latency-oriented programs
-        net = P.plan_network(geo, ntw=self.ntw, ntw0=ntw0, balanced=bal, batch_hint=batch_hint, bwd0_small=bwd0_small)
+        net = P.plan_network(geo, ntw=2, ntw0=ntw0, balanced=bal, batch_hint=batch_hint, bwd0_small=bwd0_small)
         self.dims = net["dims"]
         self.per0, self.per1, self.per2 = clip_slots(geo, net["fwd"])
         self.fwd = [_DevPlan(pl, self.device, self.prec) for pl in net["fwd"]]
@@ -354,7 +350,7 @@ class EmbedEngine:
                 raise ValueError("last_hilo is an option of the single-pass formats (%s already carries hi+lo planes)" % prec)
             import dataclasses
             pl2 = net["fwd"][2]
-            if os.environ.get("VD_L2X_PLAN", "small") == "small" and pl2.NTW == 2 and pl2.MTW == 4 and pl2.ncl % 2 == 0:
+            if pl2.NTW == 2 and pl2.MTW == 4 and pl2.ncl % 2 == 0:
                 # The hi+lo program keeps two operand planes of its patch in LDS: with the single-pass program's boxes (two clips, 4 M
                 # tiles x 2 N tiles per wave, 2 x 58 KB) only one workgroup fits a CU.  One clip per box (4 M tiles x 1 N tile per
                 # wave, 2 x 29 KB) lets two share it: 0.74 -> 0.68 ms per 512 clips, 4.53 -> 4.27 ms per launch in the bench (same
@@ -480,16 +476,6 @@ class EmbedEngine:
                 for li in range(3):
                     for dp in self.bwd[li]:
                         dp.pack(self._weights[2 * li])
-            if os.environ.get("VD_BWD_X2_SIM") == "w":
-                # measurement knob: the NUMERICS of a two-MFMA input gradient (g_hi + g_lo) x W_hi -- the low
-                # plane of the weights dropped -- at the cost of the three-MFMA program
-                if _PACK.queue:            # (inside an outer batched_packs(): the queued packs must land before their low planes are cleared)
-                    flush_packs(_PACK.queue)
-                    del _PACK.queue[:]
-                for li in range(3):
-                    for dp in self.bwd[li]:
-                        if dp.wpk.shape[0] == 2:
-                            dp.wpk[1].zero_()
             self._bwd_packed = True
 
     # ------------------------------------------------------------------------------------
@@ -607,10 +593,6 @@ class EmbedEngine:
         for li, (src, n_src, per_src, dst_ptr, n_dst, per_dst_bytes) in enumerate((
                 (act1, n1, per1, act2.data_ptr(), n2, per2 * 16), (act2, n2, per2, feats.data_ptr(), 0, self.num_feat * 4)), start=1):
             if li == 2 and hilo:                        # hi+lo weights: one set
-                if os.environ.get("VD_L2_X2_SIM") == "act":
-                    # measurement knob: the NUMERICS of a two-MFMA last level a_hi x (W_hi + W_lo) -- the low plane
-                    # of the activations dropped -- at the cost of the three-MFMA program (what the parity of such a mode would be)
-                    src[1].zero_()
                 self.fwd2x.run(src, n_src, w[5], dst_ptr, 0, None, B, out_scale=self.c8_scales if self.last_c8 else None)
             elif per % self.fwd[li].plan.ncl == 0:       # a box never spans two sets: one launch
                 self.fwd[li].run(src, n_src, w[2 * li + 1], dst_ptr, n_dst, None, B, set_clips=per,
@@ -633,8 +615,6 @@ class EmbedEngine:
             layout = 0
             for li, am in ((2, am2), (1, am1), (0, am0)):
                 dy, nslots, _, inv = self.level_unpool(li, nb, grad, layout, am)
-                if self.planes_bwd == 2 and os.environ.get("VD_BWD_X2_SIM") == "g":
-                    dy[1].zero_()      # measurement knob: the numerics of g_hi x (W_hi + W_lo)
                 grad = dx[c0:c0 + nb] if li == 0 else self.dx_buf(li, nb)
                 self.level_dgrad(self.bwd[li], dy, nslots, grad, nb, inv)
                 layout = 1

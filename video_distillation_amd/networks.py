@@ -80,7 +80,7 @@ def _weight_format():
     returned (the pooling decisions that route the gradient stay those of the exact weights): both sides of a DM class
     term then carry the same weight-rounding perturbation.  See distill.HipBackend.weight_format."""
     r, s = _PRECISION["real"], _PRECISION["syn"]
-    if r in ("f16", "bf16") and s == r + "x3" and os.environ.get("VD_VALUE_PASS", "1") == "1":
+    if r in ("f16", "bf16") and s == r + "x3":
         return r
     return None
 
@@ -518,8 +518,8 @@ class ConvNet3D(nn.Module):
         te = self._train_engine(x)
         params = list(self.parameters())
         # the weight gradients of a level run on a side stream under the input-gradient passes (5.30 -> 5.08 ms per step of 50
-        # clips); not under the class lanes of gradient matching, where the extra streams cost 4 % (VD_WGRAD_SIDE=0: off)
-        te.side_wgrad = os.environ.get("VD_WGRAD_SIDE", "1") == "1"
+        # clips); not under the class lanes of gradient matching, where the extra streams cost 4 %
+        te.side_wgrad = True
         try:
             loss, logits, grads = te.loss_and_grads(x, labels, params, self._dropout_mask(x, te))
         finally:

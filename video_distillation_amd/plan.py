@@ -396,7 +396,7 @@ def _build_type_order(box, group, row_lin, tap_list, patch_ext, mt_pad, pooled, 
 
 def _make_plan(name, src_grid, CC, row_dims, group, row_origin, row_stride, taps, widx_fn,
                n_out, NT, MW, mtw_options, epi, pool_t, relu, out_index, out_valid, n_stride,
-               out_clip_stride, out_chunk_stride, out_shape, lds_budget, ncl_options=(1,), force_box=None, ntw=1, step_multiple=1,
+               out_clip_stride, out_chunk_stride, out_shape, lds_budget, ncl_options=(1,), ntw=1, step_multiple=1,
                frame_tiles=False):
     """Generic planner.  Row (a,b,c) has its tap-(0,0,0) origin at source slot coords
     (row_stride[0]*a+row_origin[0], ...).  ``taps`` is a list of non-negative (df,dh,dw).  ``step_multiple``: pad the K steps
@@ -430,7 +430,7 @@ def _make_plan(name, src_grid, CC, row_dims, group, row_origin, row_stride, taps
                 return int(ncl * e[0] * e[1] * e[2] * 1.06) + 16
 
             try:
-                box = force_box or _choose_box(row_dims, group, rows_max, slot_fn, budget)
+                box = _choose_box(row_dims, group, rows_max, slot_fn, budget)
             except ValueError:
                 continue
             nbox = -(-row_dims[0] // box[0]) * -(-row_dims[1] // box[1]) * -(-row_dims[2] // box[2])
@@ -509,7 +509,7 @@ def _memo(fn):
     cache = {}
 
     def wrapped(*args, **kwargs):
-        key = (args, tuple(sorted(kwargs.items())), os.environ.get("VD_L0_BOX"), os.environ.get("VD_NTW2_MTW"), os.environ.get("VD_L0_FRAME_TILES"))
+        key = (args, tuple(sorted(kwargs.items())), os.environ.get("VD_L0_FRAME_TILES"))
         if key not in cache:
             cache[key] = fn(*args, **kwargs)
         return cache[key]
@@ -527,7 +527,7 @@ def plan_forward_cl(name: str, cin: int, cout: int, t_in: int, h_in: int, w_in: 
     assert cin % 8 == 0 and cout % 32 == 0
     if ntw == 2:
         assert cout == 128
-        mtw_options = tuple(int(v) for v in os.environ.get("VD_NTW2_MTW", "4").split(","))
+        mtw_options = (4,)
     CC = cin // 8
     T = conv_out_dim(t_in, KT, 1, 1); OH = conv_out_dim(h_in, KH, 2, 3); OW = conv_out_dim(w_in, KW, 2, 3)
     To, Ho, Wo = T // pool_t, OH // 2, OW // 2
@@ -783,7 +783,6 @@ def plan_forward_pix(name: str, cout: int, t_in: int, h_in: int, w_in: int, lds_
 
     def out_index(ci, a, b, c):
         return ci * clip_stride + (a * Ho + b // 2) * Wo + c // 2
-    force_box = tuple(int(v) for v in os.environ["VD_L0_BOX"].split(",")) if os.environ.get("VD_L0_BOX") else None
     plan = None
     if l0_frame_tiles() and ntw == 1 and NT == 2 and tuple(mtw_options) == (4,) and Wo % 4 == 0:
         # K order: (tap pair j, kt) for the 10 pairs of a kt plane's first 20 (c, kh) taps, then the three left-over taps
@@ -794,7 +793,7 @@ def plan_forward_pix(name: str, cout: int, t_in: int, h_in: int, w_in: int, lds_
             plan = _make_plan(name, (t_in * cin, h_in, OW), 1, rows, (1, 2, 8), (-cin, -3, 0), (cin, 2, 1), taps,
                               widx_fn, cout, NT, MW, mtw_options, EPI_POOL_CL, 1, True, out_index, None, 0,
                               clip_stride, chunk_stride, (cout // 8, T, Ho, Wo, 8), lds_budget, (1,), ntw=ntw,
-                              force_box=force_box, frame_tiles=True)
+                              frame_tiles=True)
             t0 = plan.types[0]
             plan.out_t_stride, plan.pair_flip = FRAME_TILE_OUT_STEP, FRAME_TILE_FLIP | (t0.pitch_h << 8) | (t0.pitch_f << 16)
             plan.meta["frame_tiles"] = 1
@@ -813,8 +812,7 @@ def plan_forward_pix(name: str, cout: int, t_in: int, h_in: int, w_in: int, lds_
         taps = [(kt * cin + c, kh, 0) for kt in range(KT) for c in range(cin) for kh in range(KH)]
         plan = _make_plan(name, (t_in * cin, h_in, OW), 1, rows, (2, 2, 2), (-cin, -3, 0), (cin, 2, 1), taps,
                           widx_fn, cout, NT, MW, mtw_options, EPI_POOL_CL, 1, True, out_index, None, 0,
-                          clip_stride, chunk_stride, (cout // 8, T, Ho, Wo, 8), lds_budget, (1,), ntw=ntw,
-                          force_box=force_box)
+                          clip_stride, chunk_stride, (cout // 8, T, Ho, Wo, 8), lds_budget, (1,), ntw=ntw)
         plan.out_t_stride = Ho * Wo
     plan.NTW = ntw
     rowp = pix_row_pitch(w_in)
@@ -1134,7 +1132,7 @@ _PLAN_CACHE: Dict[Tuple, Dict[str, object]] = {}
 
 
 SMALL_TILES_FIRST = (2, 4, 7, 8)
-TINY_GRID = int(os.environ.get("VD_TINY_GRID", "128"))      # latency_variant: launches below this many workgroups ignore padding (0: off)
+TINY_GRID = 128      # latency_variant: launches below this many workgroups ignore padding
 
 
 def latency_variant(pl: ConvPlan, batch_hint: Optional[int], make) -> ConvPlan:
@@ -1143,7 +1141,7 @@ def latency_variant(pl: ConvPlan, batch_hint: Optional[int], make) -> ConvPlan:
     count per wave (same padded work, more and shorter workgroups).  ``make(mtw_options)`` rebuilds the program."""
     if not batch_hint or pl.grid(batch_hint) >= 512:
         return pl
-    slack = float(os.environ.get("VD_LAT_SLACK", "1.05"))     # a few per cent of padding rows are cheaper than a long workgroup
+    slack = 1.05     # a few per cent of padding rows are cheaper than a long workgroup
     best = pl
     for opts in (SMALL_TILES_FIRST, (4,), (2,)):
         try:
@@ -1174,8 +1172,7 @@ def plan_network(geo: NetGeometry, lds_budget: int = 3700, ntw: int = 1, ntw0: i
         return _PLAN_CACHE[key]
     dims = geo.layer_dims()
     assert geo.channel == 3 and geo.pools_t[0] == 1, "first layer planner assumes RGB clips and (1,2,2) pooling"
-    fwd = [plan_forward_pix("fwd0", dims[0][1], dims[0][2], dims[0][3], dims[0][4],
-                            int(os.environ.get("VD_L0_BUDGET", lds_budget)), ntw=ntw0)]
+    fwd = [plan_forward_pix("fwd0", dims[0][1], dims[0][2], dims[0][3], dims[0][4], lds_budget, ntw=ntw0)]
     for li in (1, 2):
         cin, cout, t, h, w = dims[li][:5]
         pl = plan_forward_cl("fwd%d" % li, cin, cout, t, h, w, dims[li][11], feat_out=(li == 2), lds_budget=lds_budget)

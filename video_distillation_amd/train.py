@@ -13,7 +13,6 @@ is the module-level entry ``utils.epoch`` dispatches to.  No CPU path.
 from __future__ import annotations
 
 import contextlib
-import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -49,7 +48,7 @@ class TrainEngine:
         self.pool_kernel = tuple(int(k) for k in pool_kernel)
         self.batch_hint = batch_hint
         self.eng = EmbedEngine(geo, prec=prec, device=device, chunk=1 << 30, prec_bwd=prec_bwd, batch_hint=batch_hint,
-                               bwd0_small=os.environ.get("VD_BWD0_SMALL", "1") == "1")
+                               bwd0_small=True)
         if self.eng.planes_bwd > self.eng.planes or (prec[:2] != prec_bwd[:2]):
             raise ValueError("backward operands are read from the forward's activations: %s / %s do not combine"
                              % (prec, prec_bwd))
