@@ -393,7 +393,9 @@ int vd_head_second_order(const float* logits, const float* dlogits, const int32_
  * pixel rows; 1, 2: Conv3d(->128)+ReLU+MaxPool(2,2,2) over channels-last slots; networks.py:792-814) for clips of
  * frames x height x width and operand precision `prec`, choosing box shape, LDS pitches, wave layout and -- for
  * batch_hint > 0 clips per launch -- the latency-oriented decomposition exactly as the Python planner does, and
- * returns the serialised program (malloc'd; vd_blob_free) that vd_program_load consumes. */
+ * returns the serialised program (malloc'd; vd_blob_free) that vd_program_load consumes.  The three builders answer -2 for
+ * clips the network has no programs for, as plan.plan_network raises ValueError: an odd frame count, or a clip so small
+ * that a level pools its conv grid to nothing (4 x 32 x 32, 4 x 40 x 72). */
 int vd_program_build(int layer, int frames, int height, int width, int prec, int batch_hint, void** blob, int64_t* nbytes);
 /* the INPUT-GRADIENT programs of a level: level 0 -> one program (parity_class 0) that merges the four stride-2 parity
  * classes into the N dimension and writes fp32 pixels (T,3,H,W); levels 1, 2 -> one program per parity class

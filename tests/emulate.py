@@ -51,6 +51,8 @@ def run_plan(plan, src, w_flat, bias, nclips, out):
                     if b >= nclips:
                         continue
                     o2 = 2 * (e & 0xFFFFFF)                   # dword offset -> element offset
+                    assert 0 <= o2 and o2 + 8 <= src_flat.shape[2], \
+                        "%s box %d slot %d gathers elements [%d, %d) of a %d-element chunk" % (plan.name, bi, idx, o2, o2 + 8, src_flat.shape[2])
                     patch[idx] = src_flat[b, cc, o2:o2 + 8]
                 # A[row, s, half, j]
                 for s in range(plan.S):

@@ -24,7 +24,8 @@ def _cpp_blob(lib, layer, geo, prec, hint):
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libvd_hip.so not built")
 @pytest.mark.parametrize("dims,prec,hint", [((16, 112, 112), "f16", None), ((16, 112, 112), "f16x3", 64), ((8, 64, 64), "f16", None),
                                             ((8, 64, 64), "bf16x3", 8), ((8, 64, 64), "f16x3", 256), ((8, 80, 96), "f16", 4),
-                                            ((4, 64, 64), "f16x3", None)])
+                                            ((4, 64, 64), "f16x3", None), ((4, 64, 66), "f16", None), ((4, 64, 66), "f16x3", None),
+                                            ((4, 70, 58), "f16", None), ((4, 70, 58), "f16x3", 3)])
 def test_cpp_planner_emits_the_python_planner_s_programs(dims, prec, hint):
     lib = hip.bind(LIB)
     geo = plan.NetGeometry(*dims)
@@ -48,14 +49,16 @@ def test_cpp_planner_argument_errors():
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libvd_hip.so not built")
-@pytest.mark.parametrize("dims,hint", [((16, 112, 112), None), ((16, 112, 112), 50), ((8, 64, 64), None), ((8, 64, 64), 8), ((8, 80, 96), 4)])
+@pytest.mark.parametrize("dims,hint", [((16, 112, 112), None), ((16, 112, 112), 50), ((8, 64, 64), None), ((8, 64, 64), 8), ((8, 80, 96), 4),
+                                       ((4, 64, 66), None), ((4, 70, 58), None), ((4, 70, 58), 3)])
 def test_cpp_planner_emits_the_python_planner_s_input_gradient_programs(dims, hint, monkeypatch):
     if hint == 50:       # one combination with the 2 x 2 pixel blocks of rounds 1-3 (both planners read the same switch)
         monkeypatch.setenv("VD_BWD0_WIDE", "0")
     lib = hip.bind(LIB)
     geo = plan.NetGeometry(*dims)
     net = plan.plan_network(geo, ntw=2, ntw0=1, balanced=True, batch_hint=hint)
-    assert net["bwd"][0][0].meta["block_w"] == (2 if hint == 50 else 4) and net["bwd"][0][0].n_out == (12 if hint == 50 else 24)
+    narrow = hint == 50 or dims[2] % 4 != 0          # (widths that are no multiple of 4 have the 2 x 2 blocks only)
+    assert net["bwd"][0][0].meta["block_w"] == (2 if narrow else 4) and net["bwd"][0][0].n_out == (12 if narrow else 24)
     for layer in range(3):
         for cls, pl in enumerate(net["bwd"][layer]):
             want = plan.export_program(pl)
@@ -69,6 +72,51 @@ def test_cpp_planner_emits_the_python_planner_s_input_gradient_programs(dims, hi
             assert got == want, "dgrad layer %d class %d differs" % (layer, cls)
         blob, n = ctypes.c_void_p(), ctypes.c_int64()
         assert lib.vd_program_build_dgrad(layer, len(net["bwd"][layer]), geo.frames, geo.height, geo.width, 0, ctypes.byref(blob), ctypes.byref(n)) == -3
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libvd_hip.so not built")
+@pytest.mark.parametrize("dims", [(4, 63, 64), (4, 65, 63)])
+def test_cpp_planner_at_odd_clip_sizes_has_every_program_but_the_first_level_input_gradient(dims):
+    """The documented limit of the C++ twin (planner.cpp, plan_dgrad_layer: "odd clip sizes: Python planner only"): at an odd clip
+    height or width the Python planner splits the first level's input gradient into four parity-class programs with pixel output,
+    which the C++ planner does not build -- -3 for every class.  Everything else is byte-identical: the forward programs of all
+    three levels in both precision families, and the input-gradient programs of levels 1 and 2."""
+    lib = hip.bind(LIB)
+    geo = plan.NetGeometry(*dims)
+    for prec in ("f16", "f16x3"):
+        net = plan.plan_network(geo, ntw=2, ntw0=1, balanced=not prec.endswith("x3"))
+        for layer in range(3):
+            assert _cpp_blob(lib, layer, geo, prec, None) == plan.export_program(net["fwd"][layer]), (prec, layer)
+    net = plan.plan_network(geo, ntw=2, ntw0=1, balanced=True)
+    assert [len(l) for l in net["bwd"]] == [4, 4, 4] and all(pl.n_stride == dims[1] * dims[2] for pl in net["bwd"][0])
+    for layer in range(3):
+        for cls, pl in enumerate(net["bwd"][layer]):
+            blob, n = ctypes.c_void_p(), ctypes.c_int64()
+            rc = lib.vd_program_build_dgrad(layer, cls, geo.frames, geo.height, geo.width, 0, ctypes.byref(blob), ctypes.byref(n))
+            if layer == 0:
+                assert rc == -3, (cls, rc)
+                continue
+            assert rc == 0, (layer, cls, rc)
+            try:
+                got = ctypes.string_at(blob, n.value)
+            finally:
+                lib.vd_blob_free(blob)
+            assert got == plan.export_program(pl), "dgrad layer %d class %d differs" % (layer, cls)
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libvd_hip.so not built")
+@pytest.mark.parametrize("dims", [(4, 32, 32), (4, 40, 72), (2, 64, 64), (5, 64, 64), (16, 8, 8)])
+def test_both_planners_refuse_the_same_clips(dims):
+    """Clips without three pooled levels and odd frame counts: -2 from the three C++ builders at every level, ValueError from
+    plan.plan_network."""
+    lib = hip.bind(LIB)
+    blob, n, block, reps = ctypes.c_void_p(), ctypes.c_int64(), (ctypes.c_int * 3)(), ctypes.c_int()
+    for layer in range(3):
+        assert lib.vd_program_build(layer, *dims, 1, 0, ctypes.byref(blob), ctypes.byref(n)) == -2
+        assert lib.vd_program_build_dgrad(layer, 0, *dims, 0, ctypes.byref(blob), ctypes.byref(n)) == -2
+        assert lib.vd_program_build_wgrad(layer, *dims, 4, 1, ctypes.byref(blob), ctypes.byref(n), block, ctypes.byref(reps)) == -2
+    with pytest.raises(ValueError, match="%d x %d x %d" % dims):
+        plan.plan_network(plan.NetGeometry(*dims), ntw=2, ntw0=1, balanced=True)
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libvd_hip.so not built")

@@ -230,6 +230,88 @@ def test_odd_geometry_floor_pooling_and_multi_type_boxes():
                 np.testing.assert_allclose(out.reshape(1,t_,cin,h,w).transpose(0,2,1,3,4),want.numpy(),rtol=1e-9,atol=1e-9)
 
 
+@pytest.mark.parametrize("dims", [(4, 64, 66), (4, 65, 63), (4, 70, 58)])
+def test_clip_sizes_off_the_multiple_of_four(dims):
+    """Clip sizes with W % 4 != 0 or odd H / W, planned as EmbedEngine plans them (ntw = 2, ntw0 = 1, balanced): the program
+    families no even, W % 4 == 0 clip reaches --
+      4 x 64 x 66: level-0 input gradient merged in 2 x 2 pixel blocks (two box types), 32 x 33 conv grid pooled by floor;
+      4 x 65 x 63: level-0 input gradient as four parity-class programs with pixel output, one-type frame-tile forward at width 63;
+      4 x 70 x 58: four-type level-0 forward without frame tiles, (MW, MTW) = (1, 2) level-1 forward, level-2 parity classes of
+                   32 / 64 / 32 / 64 clips per box.
+    Level-0 / level-1 forward and every input-gradient program against fp64 conv3d / autograd; the input gradients of levels 1
+    and 2 with ncl + 1 clips (largest ncl of the level's programs), so that every program's last clip group is ragged."""
+    geo = P.NetGeometry(*dims)
+    net = P.plan_network(geo, ntw=2, ntw0=1, balanced=True)
+    f0, b0, b2 = net["fwd"][0], net["bwd"][0], net["bwd"][2]
+    if dims == (4, 64, 66):
+        assert len(b0) == 1 and b0[0].meta["block_w"] == 2 and b0[0].n_out == 12 and len(b0[0].types) == 2
+        assert net["dims"][0][6:8] == (32, 33)
+    elif dims == (4, 65, 63):
+        assert [p.MTW for p in b0] == [2, 2, 8, 8] and sum(len(p.types) == 2 for p in b0) == 3 and all(p.n_stride == 65 * 63 for p in b0)
+        assert f0.meta.get("frame_tiles") == 1 and len(f0.types) == 1 and net["dims"][0][6:8] == (33, 32)
+    else:
+        assert len(f0.types) == 4 and "frame_tiles" not in f0.meta and (net["fwd"][1].MW, net["fwd"][1].MTW) == (1, 2)
+        assert [p.ncl for p in b2] == [32, 64, 32, 64] and [p.MTW for p in b2] == [8, 4, 8, 2]
+    g = torch.Generator().manual_seed(sum(dims))
+    params = [p.double() for p in R.init_params(5)]
+    x = torch.randn(1, dims[0], 3, dims[1], dims[2], generator=g).double()
+    col = []
+    R.feature_layers(x.permute(0, 2, 1, 3, 4), params, collect=col)
+    out = np.zeros(int(np.prod(f0.out_shape)))
+    E.run_plan(f0, E.pix_to_rows(x.numpy()), params[0].numpy().ravel(), params[1].numpy(), 1, out)
+    np.testing.assert_allclose(cl_to_bcthw(out, 1, f0.out_shape), col[2].numpy(), rtol=1e-9, atol=1e-9)
+    f1 = net["fwd"][1]
+    out = np.zeros(int(np.prod(f1.out_shape)))
+    E.run_plan(f1, bcthw_to_cl(col[2].numpy()), params[2].numpy().ravel(), params[3].numpy(), 1, out)
+    np.testing.assert_allclose(cl_to_bcthw(out, 1, f1.out_shape), col[5].numpy(), rtol=1e-9, atol=1e-9)
+    for li in range(3):
+        cin, cout, t, h, w, T, OH, OW = net["dims"][li][:8]
+        n = max(p.ncl for p in net["bwd"][li]) + 1 if li > 0 else 1
+        dy = torch.randn(n, cout, T, OH, OW, generator=g).double()
+        xin = torch.zeros(n, cin, t, h, w, dtype=torch.double, requires_grad=True)
+        (want,) = torch.autograd.grad(F.conv3d(xin, params[2 * li], None, stride=(1, 2, 2), padding=(1, 3, 3)), xin, dy)
+        out = np.full(n * cin * t * h * w, np.nan)      # (the programs of a level store: together they must write every element)
+        for pl in net["bwd"][li]:
+            E.run_plan(pl, bcthw_to_cl(dy.numpy()), params[2 * li].numpy().ravel(), None, n, out)
+        got = out.reshape(n, t, cin, h, w).transpose(0, 2, 1, 3, 4) if li == 0 else out.reshape(n, t, h, w, cin).transpose(0, 4, 1, 2, 3)
+        np.testing.assert_allclose(got, want.numpy(), rtol=1e-9, atol=1e-9)
+        if li == 0 and dims == (4, 64, 66):      # ... and the training engines' small-box form of the merged program
+            small = P.plan_network(geo, ntw=2, ntw0=1, balanced=True, bwd0_small=True)["bwd"][0][0]
+            assert small.MTW == 4 and small.lds_slots <= 1800 and small.nbox > b0[0].nbox
+            out = np.full(cin * t * h * w, np.nan)
+            E.run_plan(small, bcthw_to_cl(dy.numpy()), params[0].numpy().ravel(), None, 1, out)
+            np.testing.assert_allclose(out.reshape(1, t, cin, h, w).transpose(0, 2, 1, 3, 4), want.numpy(), rtol=1e-9, atol=1e-9)
+
+
+def test_gather_outside_the_clip_is_an_error_of_the_emulator():
+    """A gather table that reads past the end of a clip's chunk must fail on the CPU (numpy would silently shorten the slice)."""
+    import dataclasses
+    pl = P.plan_network(GEO)["bwd"][2][0]
+    cin, cout, t, h, w, T, OH, OW = P.plan_network(GEO)["dims"][2][:8]
+    src = np.zeros((1, cout // 8, T, OH, OW, 8))
+    wts = np.zeros(cout * cin * 3 * 7 * 7)
+    E.run_plan(pl, src, wts, None, 1, np.zeros(cin * t * h * w))
+    gt = pl.gather_table().copy()
+    slot = np.argwhere((gt >= 0) & (gt >> 24 == 0))[-1]                                 # (a slot of the group's first clip)
+    gt[slot[0], slot[1]] = (gt[slot[0], slot[1]] & ~0xFFFFFF) | (T * OH * OW * 4)       # one slot past the chunk's last
+    bad = dataclasses.replace(pl)
+    bad.gather_table = lambda: gt
+    with pytest.raises(AssertionError, match="gathers elements"):
+        E.run_plan(bad, src, wts, None, 1, np.zeros(cin * t * h * w))
+
+
+@pytest.mark.parametrize("dims,why", [((4, 32, 32), "level 2"), ((4, 40, 72), "level 2"), ((16, 8, 8), "level 1"), ((2, 64, 64), "level 2"),
+                                      ((5, 64, 64), "even"), ((3, 64, 64), "even")])
+def test_clips_too_small_or_with_an_odd_frame_count_are_refused_by_name(dims, why):
+    """Clips that leave a level without a pooled output, and odd frame counts, have no tile programs: a ValueError that names the
+    geometry and the reason (vd_program_build refuses the smallest of them with -2), not a ZeroDivisionError or a bare assertion."""
+    with pytest.raises(ValueError, match=r"%d x %d x %d clips.*%s" % (dims + (why,))):
+        P.plan_network(P.NetGeometry(*dims), ntw=2, ntw0=1, balanced=True)
+    with pytest.raises(ValueError):
+        P.plan_network(P.NetGeometry(*dims))
+    assert P.plan_network(P.NetGeometry(4, 48, 48))["dims"][2][8:11] == (1, 1, 1)       # (a small clip that does plan)
+
+
 def test_exported_program_blob_layout():
     """plan.export_program: 40 int64 header words + the int32 arrays whose lengths the header lists
     (what vd_program_load in csrc/program.hip parses)."""
@@ -249,7 +331,7 @@ def test_exported_program_blob_layout():
         assert h[22] == pl.ncl and h[23] == pl.nbox and h[24] == pl.gather_table().shape[1]
 
 
-@pytest.mark.parametrize("geom", [(16, 112, 112), (8, 64, 64), (12, 96, 80), (6, 48, 64), (10, 40, 48)])
+@pytest.mark.parametrize("geom", [(16, 112, 112), (8, 64, 64), (12, 96, 80), (6, 48, 64), (10, 40, 48), (4, 64, 66), (4, 65, 63)])
 def test_first_level_frame_tiles_have_the_structure_the_sharing_kernel_relies_on(geom):
     """plan_forward_pix (round 5): wherever the pooled width is a multiple of 4 the first level is planned in FRAME TILES -- the four
     M tiles of a wave row are the same 32 positions in consecutive frames, K step 3 j + kt holds tap pair j of kernel plane kt with

@@ -907,11 +907,20 @@ std::vector<uint8_t> export_program(const Plan& pl, int persist) {
     return blob;
 }
 
+// plan.plan_network's refusal: an odd frame count (the first-layer planner pairs frames) or a clip so small that one of the
+// three levels pools its conv grid to nothing has no tile programs (ValueError there, -2 here)
+bool clip_has_programs(int frames, int height, int width) {
+    if (frames % 2 != 0) return false;
+    int cin, t, h, w;
+    layer_input(3, frames, height, width, cin, t, h, w);      // (extent of the features)
+    return t >= 1 && h >= 1 && w >= 1;
+}
+
 }  // namespace
 
 extern "C" int vd_program_build(int layer, int frames, int height, int width, int prec, int batch_hint, void** blob, int64_t* nbytes) {
     if (blob == nullptr || nbytes == nullptr || layer < 0 || layer > 2 || prec < 0 || prec > 3) return -1;
-    if (frames < 2 || height < 16 || width < 16) return -2;
+    if (frames < 2 || height < 16 || width < 16 || !clip_has_programs(frames, height, width)) return -2;
     Plan pl;
     if (!plan_layer(layer, frames, height, width, prec, batch_hint, pl)) return -3;
     const std::vector<uint8_t> b = export_program(pl, VD_BOX_WALK_GENERATIONS);
@@ -926,7 +935,7 @@ extern "C" int vd_program_build(int layer, int frames, int height, int width, in
 extern "C" int vd_program_build_dgrad(int layer, int parity_class, int frames, int height, int width, int batch_hint, void** blob,
                                       int64_t* nbytes) {
     if (blob == nullptr || nbytes == nullptr || layer < 0 || layer > 2) return -1;
-    if (frames < 2 || height < 16 || width < 16) return -2;
+    if (frames < 2 || height < 16 || width < 16 || !clip_has_programs(frames, height, width)) return -2;
     Plan pl;
     if (!plan_dgrad_layer(layer, parity_class, frames, height, width, batch_hint, pl)) return -3;
     const std::vector<uint8_t> b = export_program(pl, VD_BOX_WALK_GENERATIONS);
@@ -941,7 +950,7 @@ extern "C" int vd_program_build_dgrad(int layer, int parity_class, int frames, i
 extern "C" int vd_program_build_wgrad(int layer, int frames, int height, int width, int nclips, int planes, void** blob,
                                       int64_t* nbytes, int* block3, int* replicas) {
     if (blob == nullptr || nbytes == nullptr || block3 == nullptr || replicas == nullptr || layer < 0 || layer > 2) return -1;
-    if (frames < 2 || height < 16 || width < 16 || nclips < 1 || planes < 1 || planes > 2) return -2;
+    if (frames < 2 || height < 16 || width < 16 || !clip_has_programs(frames, height, width) || nclips < 1 || planes < 1 || planes > 2) return -2;
     int cin, t, h, w;
     layer_input(layer, frames, height, width, cin, t, h, w);
     const int cout = layer == 0 ? 64 : 128;

@@ -1172,6 +1172,13 @@ def plan_network(geo: NetGeometry, lds_budget: int = 3700, ntw: int = 1, ntw0: i
         return _PLAN_CACHE[key]
     dims = geo.layer_dims()
     assert geo.channel == 3 and geo.pools_t[0] == 1, "first layer planner assumes RGB clips and (1,2,2) pooling"
+    if geo.frames % 2 != 0:
+        raise ValueError("no tile programs for %d x %d x %d clips: the frame count must be even (the first-layer planner pairs frames)"
+                         % (geo.frames, geo.height, geo.width))
+    for li, d in enumerate(dims):
+        if min(d[8:11]) < 1:      # (vd_program_build answers -2 for the same clips)
+            raise ValueError("no tile programs for %d x %d x %d clips: level %d pools its %d x %d x %d conv grid to %d x %d x %d, "
+                             "nothing is left for %d levels" % (geo.frames, geo.height, geo.width, li, d[5], d[6], d[7], d[8], d[9], d[10], len(dims)))
     fwd = [plan_forward_pix("fwd0", dims[0][1], dims[0][2], dims[0][3], dims[0][4], lds_budget, ntw=ntw0)]
     for li in (1, 2):
         cin, cout, t, h, w = dims[li][:5]
