@@ -41,6 +41,20 @@ def save_s2d(save_dir: str, it: int, dynamic_syn: torch.Tensor, hal_weights: Seq
         torch.save(state, os.path.join(save_dir, "weights_best.pt"))
 
 
+def save_static(save_dir: str, it: int, static_syn: torch.Tensor, best: bool = False) -> str:
+    """``static_{it}.pt`` / ``static_best.pt``: ``{"image": (C*spc,3,H,W)}``, row ``c*spc + j`` -- the file ``load_static`` and the
+    reference's ``torch.load(path)["image"]`` read (``run_dc --memories static`` writes it)."""
+    if static_syn.dim() != 4 or static_syn.shape[1] != 3:
+        raise ValueError("save_static: a (C*spc, 3, H, W) tensor, not %s" % (tuple(static_syn.shape),))
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, "static_%d.pt" % it)
+    blob = {"image": static_syn.detach().cpu().clone()}
+    torch.save(blob, path)
+    if best:
+        torch.save(blob, os.path.join(save_dir, "static_best.pt"))
+    return path
+
+
 def load_static(path: str) -> torch.Tensor:
     """Static memory as the reference loads it: a dict with key "image" -> (C*spc,3,H,W)."""
     obj = torch.load(path, map_location="cpu")

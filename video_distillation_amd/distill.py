@@ -1068,6 +1068,14 @@ class HipGMOps:
         hip = self.hip
         hip.run("vd_sgd_momentum", hip.ptr(x), hip.ptr(buf), hip.ptr(g), x.numel(), lr, mu, int(first), hip.stream_ptr(self.device))
 
+    def still_expand(self, images, index, T: int):
+        """Still clips of the rows ``index`` (None: all) on the current stream.  A device ``index`` is passed as it is: the
+        trainer's rows come from ``sample_real_indices`` over class ranges ``StillGMTrainer`` checked against the pool."""
+        return self.hip.still_expand(images, index, T, checked=True)
+
+    def still_reduce(self, g_clips):
+        return self.hip.still_reduce(g_clips.contiguous())
+
     def train_epoch(self, net, images, labels, optimizer, batch_train: int):
         import types
         from . import utils
@@ -1151,14 +1159,14 @@ class GMTrainer:
                     with torch.cuda.stream(lanes[lane]):
                         if gsz > 1 and k % gsz == 0:
                             k1 = min(k + gsz, ncls)
-                            real_all = self.pool.clips[idx_t[k:k1].reshape(-1)]
+                            real_all = self._real_batch(idx_t[k:k1].reshape(-1))
                             # (labels built ON the device: an upload here would be a blocking copy on a busy lane stream)
                             lab_all = torch.cat([torch.full((idx_t.shape[1],), cc, dtype=torch.int64, device=dev) for cc in self.classes[k:k1]])
                             grouped = dict(zip(range(k, k1), ops.param_grads_grouped(net, real_all, lab_all, k1 - k, slot=lane)))
                         if gsz > 1:
                             gw_real = grouped.pop(k)
                         else:
-                            real = self.pool.clips[idx_t[k]]
+                            real = self._real_batch(idx_t[k])
                             lab_r = torch.full((real.shape[0],), c, dtype=torch.int64, device=dev)
                             gw_real = [t.detach() for t in ops.param_grads(net, real, lab_r, False, slot=lane)]
                         lab_s = torch.full((self.ipc,), c, dtype=torch.int64, device=dev)
@@ -1174,7 +1182,7 @@ class GMTrainer:
                 total = total + torch.stack(totals).sum()
             else:
                 total = total + self._class_terms_serial(ops, net, idx_t, g_img, dev)
-            ops.sgd(self.image_syn, self.buf, g_img, self.lr_img, self.momentum, first=(self.steps_done == 0))
+            self._apply_pixel_grad(g_img)
             self.steps_done += 1
             if ol == self.outer_loop - 1:
                 break
@@ -1192,7 +1200,7 @@ class GMTrainer:
 
         def real_side(k):
             c = self.classes[k]
-            real = self.pool.clips[idx_t[k]]
+            real = self._real_batch(idx_t[k])
             lab_r = torch.full((real.shape[0],), c, dtype=torch.int64, device=dev)
             if overlap:
                 return ops.param_grads_async(net, real, lab_r)
@@ -1221,6 +1229,95 @@ class GMTrainer:
         return local_loss
 
     gather_syn = DMTrainer.gather_syn
+
+    # -- what differs between clips and still images (StillGMTrainer) ------------------------------------------------------
+    def _real_batch(self, idx: torch.Tensor) -> torch.Tensor:
+        """The real clips of the pool rows ``idx`` (a device tensor)."""
+        return self.pool.clips[idx]
+
+    def _apply_pixel_grad(self, g_img: torch.Tensor) -> None:
+        """One optimiser step on the synthetic pixels with the gradient ``g_img`` of all owned clips."""
+        self.ops.sgd(self.image_syn, self.buf, g_img, self.lr_img, self.momentum, first=(self.steps_done == 0))
+
+
+def still_expand(ops, images: torch.Tensor, index: Optional[torch.Tensor], T: int) -> torch.Tensor:
+    """(N,3,H,W) -> (n,T,3,H,W) still clips of the rows ``index`` (None: all, in order): ``ops.still_expand`` where the ops
+    have one (HipGMOps: ``vds_still_expand``), the torch expression otherwise (the CPU oracle ops)."""
+    if hasattr(ops, "still_expand"):
+        return ops.still_expand(images, index, T)
+    x = images if index is None else images[index]
+    return x.unsqueeze(1).expand(-1, T, -1, -1, -1).contiguous()
+
+
+def still_reduce(ops, g_clips: torch.Tensor) -> torch.Tensor:
+    """(n,T,3,H,W) -> (n,3,H,W): the sum over the frames in ascending t, one fp32 add per frame (``ops.still_reduce`` /
+    ``vds_still_reduce``, or the same adds in torch)."""
+    if hasattr(ops, "still_reduce"):
+        return ops.still_reduce(g_clips)
+    out = g_clips[:, 0].clone()
+    for t in range(1, g_clips.shape[1]):
+        out = out + g_clips[:, t]
+    return out
+
+
+class StillGMTrainer(GMTrainer):
+    """Gradient matching on STILL clips: the static-learning stage of the static + dynamic method.  The memories are
+    ``static`` (n_owned*spc, 3, H, W) images; the network is the hot path's ConvNet3D, fed each image repeated over the
+    ``geo.frames`` frames -- what the reference's ``static*`` datasets hand to ConvNet3D (distill_utils/dataset.py:626-633)
+    and what the hallucinator's static branch feeds it in the next stage.  (Upstream DC learns its images on a 2-D ConvNet;
+    this project has no 2-D network on the HIP path: DESIGN section 16.)
+
+    ``pool.clips`` holds stills (N, 3, H, W), a sixteenth of a clip pool's HBM.  Per outer iteration:
+    ``image_syn = expand(static)``, a real batch is ``expand(pool, idx)``, the pixel gradient (n, T, 3, H, W) is summed over
+    T in ascending t (``still_reduce``) and applied to ``static`` by the same SGD-with-momentum kernel as the clips' step.
+
+    Exact pooling ties are the normal case here: the frames of a still clip are equal, interior frames stay equal after
+    every level, so the temporal max-pool sees exact ties wherever it looks at two of them.  Which of two EQUAL frames a
+    pool picks moves gradient between frames of one clip and nothing else: every frame is the same function of the
+    image, so after the sum over T the image gradient is the same, and the parameter gradients (sums over all positions)
+    are too.  tests/test_gpu_still.py checks this against clips without ties instead of assuming it."""
+
+    def __init__(self, ops, pool: RealPool, geo: P.NetGeometry, num_classes: int, spc: int, batch_real: int, lr_img: float,
+                 lr_net: float = 0.01, momentum: float = 0.5, rank: int = 0, world: int = 1,
+                 static: Optional[torch.Tensor] = None, outer_loop: int = 1, inner_loop: int = 1, batch_train: int = 256,
+                 dropout_p: Optional[float] = None, net_init=None):
+        stills = pool.clips
+        if stills.dim() != 4 or tuple(stills.shape[1:]) != (3, geo.height, geo.width):
+            raise ValueError("StillGMTrainer: a pool of stills (N, 3, %d, %d), not %s" % (geo.height, geo.width, tuple(stills.shape)))
+        c_lo, c_hi = class_range(num_classes, rank, world)
+        for c in range(c_lo, c_hi):          # (every index sample_real_indices draws lies in the pool: the kernel does not check)
+            if pool.offsets[c] < 0 or pool.offsets[c] + pool.counts[c] > stills.shape[0]:
+                raise ValueError("StillGMTrainer: class %d occupies rows %d..%d of a pool of %d stills"
+                                 % (c, pool.offsets[c], pool.offsets[c] + pool.counts[c], stills.shape[0]))
+        if static is None:          # --init real: the first spc stills of each owned class
+            idx = np.concatenate([pool.offsets[c] + np.arange(spc) % pool.counts[c] for c in range(c_lo, c_hi)]) \
+                if c_hi > c_lo else np.zeros(0, dtype=np.int64)
+            static = stills[torch.as_tensor(idx, device=stills.device, dtype=torch.int64)].clone()
+        if tuple(static.shape) != ((c_hi - c_lo) * spc, 3, geo.height, geo.width):
+            raise ValueError("StillGMTrainer: static %s for %d owned classes x spc %d" % (tuple(static.shape), c_hi - c_lo, spc))
+        self.static = static.contiguous()
+        self.spc = int(spc)
+        super().__init__(ops, pool, geo, num_classes, spc, batch_real, lr_img, lr_net=lr_net, momentum=momentum, rank=rank,
+                         world=world, image_syn=still_expand(ops, self.static, None, geo.frames), outer_loop=outer_loop,
+                         inner_loop=inner_loop, batch_train=batch_train, dropout_p=dropout_p, net_init=net_init)
+        self.buf = torch.zeros_like(self.static)          # momentum of the IMAGES (the base class made one of the clips' size)
+
+    def _real_batch(self, idx: torch.Tensor) -> torch.Tensor:
+        return still_expand(self.ops, self.pool.clips, idx, self.geo.frames)
+
+    def _apply_pixel_grad(self, g_img: torch.Tensor) -> None:
+        g_static = still_reduce(self.ops, g_img)
+        self.ops.sgd(self.static, self.buf, g_static, self.lr_img, self.momentum, first=(self.steps_done == 0))
+        self.image_syn = still_expand(self.ops, self.static, None, self.geo.frames)          # the clips of the next outer iteration
+
+    def gather_static(self) -> torch.Tensor:
+        """All ranks' images in class order on every rank: row ``c*spc + j``, the layout ``static_idx = spc*label + ...``
+        of the s2d stage reads (``static_*.pt``)."""
+        if not collectives_on(self.world):
+            return self.static
+        import types
+        return DMTrainer.gather_syn(types.SimpleNamespace(world=self.world, num_classes=self.num_classes, ipc=self.spc,
+                                                          image_syn=self.static))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -19,11 +19,12 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvd_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernels.hip", "program.hip", "planner.cpp", "comm.cpp",
-                                                         "coreset.hip", "clips_sample.hip", "eval_stats.hip", "traj.hip")]
+                                                         "coreset.hip", "clips_sample.hip", "eval_stats.hip", "still.hip", "traj.hip")]
 CSRC_HEADERS = [os.path.join(_HERE, "csrc", "frame_norm.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
 HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
 HEADER_TRAJ = os.path.join(_HERE, "..", "include", "vd_traj.h")      # the second public header: the vdt_ entry points (csrc/traj.hip)
+HEADER_STILL = os.path.join(_HERE, "..", "include", "vd_still.h")      # the third: the vds_ entry points (csrc/still.hip)
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
@@ -121,7 +122,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER, HEADER_TRAJ, *CSRC_HEADERS)
+        key = _file_hash(src, HEADER, HEADER_TRAJ, HEADER_STILL, *CSRC_HEADERS)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -166,12 +167,12 @@ def library_stamp(path: str = None) -> Optional[str]:
 
 
 def sources_hash() -> str:
-    """sha256 (first 16 hex digits) over the kernel sources and the two ABI headers: what measurement files that are carried from one
+    """sha256 (first 16 hex digits) over the kernel sources and the three ABI headers: what measurement files that are carried from one
     run to the next (profiles/rNN_pmc_traffic.json -> bench.py's ``roofline.traffic``) are stamped with, so that a figure
     measured on other kernels is refused instead of quoted."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER, HEADER_TRAJ] + CSRC_HEADERS:
+    for path in sorted(SOURCES) + [HEADER, HEADER_TRAJ, HEADER_STILL] + CSRC_HEADERS:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -179,13 +180,13 @@ def sources_hash() -> str:
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
 _RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None, "const char*": ctypes.c_char_p}
-_PROTOTYPE = re.compile(r"(int64_t|int|void|const char\s*\*)\s*(vdt?_[a-z0-9_]+)\s*\(([^()]*)\)")
+_PROTOTYPE = re.compile(r"(int64_t|int|void|const char\s*\*)\s*(vd[ts]?_[a-z0-9_]+)\s*\(([^()]*)\)")
 _PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+")
 
 
 def parse_header(text: str, where: str = "include/vd_hip.h") -> dict:
-    """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses (names ``vd_*``, or ``vdt_*`` for
-    include/vd_traj.h) -> {name: (restype, [argtypes])}.  Anything else -- a type outside the set, a statement that is not wholly
+    """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses (names ``vd_*``, ``vdt_*`` for
+    include/vd_traj.h, ``vds_*`` for include/vd_still.h) -> {name: (restype, [argtypes])}.  Anything else -- a type outside the set, a statement that is not wholly
     a prototype -- is a ``ValueError`` that quotes it; no guesses."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"typedef\s+struct\s*\w*\s*(\{[^{}]*\}\s*)?\w+\s*;", " ", text)
@@ -225,6 +226,17 @@ def signatures_ext() -> dict:
     return sigs
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_still() -> dict:
+    """{name: (restype, [argtypes])} of include/vd_still.h, the ``vds_`` entry points of the same library."""
+    with open(HEADER_STILL) as f:
+        sigs = parse_header(f.read(), "include/vd_still.h")
+    other = [name for name in sigs if not name.startswith("vds_")]
+    if other:
+        raise ValueError("include/vd_still.h declares %s: its entry points carry the prefix vds_" % ", ".join(other))
+    return sigs
+
+
 def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
     if name == "EXPORTS":
         return tuple(signatures())
@@ -239,10 +251,10 @@ class _Library(ctypes.CDLL):
 
 
 def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
-    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h and
-    include/vd_traj.h."""
+    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h,
+    include/vd_traj.h and include/vd_still.h."""
     L = _Library(path)
-    for name, (restype, argtypes) in list(signatures().items()) + list(signatures_ext().items()):
+    for name, (restype, argtypes) in list(signatures().items()) + list(signatures_ext().items()) + list(signatures_still().items()):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -434,6 +446,57 @@ def hallucinate_multi(static: torch.Tensor, dynamic: torch.Tensor, sidx, didx, h
         run("vd_hallucinator_fwd_multi", ptr(static), ptr(dynamic), base, base + o_d, base + o_h, ptr(weights), ptr(biases), nh, n,
             T, H, W, ptr(out), stream_ptr(dev))
     return out if e is None else (out, tab[o_e:o_h].view(torch.int64))
+
+
+def _still_tensor(t: torch.Tensor, dims: int, what: str) -> None:
+    if t.dim() != dims or int(t.shape[-3]) != 3:
+        raise ValueError("%s: a (%s3, H, W) tensor, not %s" % (what, "n, " if dims == 4 else "n, T, ", tuple(t.shape)))
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise RuntimeError("%s has no CPU path: a contiguous fp32 tensor on a HIP device" % what)
+
+
+def still_expand(images: torch.Tensor, index, T: int, checked: bool = False) -> torch.Tensor:
+    """``vds_still_expand`` on the current stream: -> a fresh (n, T, 3, H, W) tensor, out[i, t] = images[index[i]] (``index``
+    None: out[i, t] = images[i]).  ``images`` (N, 3, H, W) contiguous fp32 on a HIP device.  ``index`` may repeat rows; a HOST
+    table (array, list, CPU tensor) is checked here and uploaded with one copy, a device tensor is checked with one device
+    reduction (a host read) unless the caller says it has ``checked`` it.  ``ValueError`` for a row outside [0, N): it never
+    reaches the kernel, which does not check."""
+    import numpy as np
+    _still_tensor(images, 4, "still_expand: images")
+    N, H, W, T = int(images.shape[0]), int(images.shape[2]), int(images.shape[3]), int(T)
+    if T < 1 or H < 1 or W < 1:
+        raise ValueError("still_expand: T %d, H %d, W %d" % (T, H, W))
+    dev = images.device
+    if index is None:
+        n, idx = N, None
+    else:
+        if isinstance(index, torch.Tensor) and index.is_cuda:
+            idx = index.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+            bad = bool(((idx < 0) | (idx >= N)).any()) if idx.numel() and not checked else False
+        else:
+            host = np.ascontiguousarray(np.asarray(index, dtype=np.int64).reshape(-1))
+            bad = bool(host.size) and (int(host.min()) < 0 or int(host.max()) >= N)
+            idx = None if bad else torch.as_tensor(host).to(dev)
+        if bad:
+            raise ValueError("still_expand: an index outside [0, %d)" % N)
+        n = int(idx.numel())
+    out = torch.empty((n, T, 3, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        run("vds_still_expand", ptr(images), ptr(idx), n, T, H, W, ptr(out), stream_ptr(dev))
+    return out
+
+
+def still_reduce(g_clips: torch.Tensor) -> torch.Tensor:
+    """``vds_still_reduce`` on the current stream: (n, T, 3, H, W) -> a fresh (n, 3, H, W) tensor, the sum over the frames in
+    ascending t, one fp32 add per frame (bitwise repeatable)."""
+    _still_tensor(g_clips, 5, "still_reduce: g_clips")
+    n, T, _, H, W = (int(v) for v in g_clips.shape)
+    if T < 1 or H < 1 or W < 1:
+        raise ValueError("still_reduce: T %d, H %d, W %d" % (T, H, W))
+    out = torch.empty((n, 3, H, W), dtype=torch.float32, device=g_clips.device)
+    with torch.cuda.device(g_clips.device):
+        run("vds_still_reduce", ptr(g_clips), n, T, H, W, ptr(out), stream_ptr(g_clips.device))
+    return out
 
 
 class Comm:

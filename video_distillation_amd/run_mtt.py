@@ -11,6 +11,9 @@ branch reads.
         --dpc 2 --path_static static.pt --no_train_static --lr_dynamic 1e4 --lr_hal 1e-3 --train_lr
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m video_distillation_amd.run_mtt ...
 
+``static.pt``: ``python -m video_distillation_amd.run_dc --memories static --dataset singleUCF50 --data_path D --spc 2`` writes it
+as ``static_best.pt`` / ``static_{it}.pt``.
+
 The expert trajectories of ``--buffer_path`` (``replay_buffer_N.pt`` of buffer.py) are served by ``experts.ExpertStore``:
 ``--expert_store host`` keeps one file at a time in pinned host memory, ``resident`` all of them in HBM; ``--buffer_walk all``
 visits every file, ``reference`` only the first of the shuffle, as the reference's loops do (they never load a second file);

@@ -6,6 +6,9 @@ distill_s2d_ms.py:312-445, with its flag names and defaults for everything that 
         --vpc 1 --spc 2 --dpc 2 --lr_dynamic=1e-3 --lr_hal=1e-5
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m video_distillation_amd.run_s2d ...
 
+``static.pt`` is what ``python -m video_distillation_amd.run_dc --memories static --dataset singleUCF50 --data_path D --spc 2``
+writes as ``static_best.pt`` / ``static_{it}.pt`` (or the file the reference offers for download).
+
 Data as ``run_dm`` (``run_dm.load_data``: ``--dataset synthetic``, the reference's frame folders, or ``--data_file f.pt``); process
 setup, log, evaluation round and the project's own flags are ``driver.py``'s.  The static memory comes
 from ``--path_static`` (a dict with key "image", (C*spc,3,H,W)) or seeded noise; the dynamic memory (C,dpc,T,1,H,W) is seeded
