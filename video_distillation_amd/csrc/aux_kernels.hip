@@ -7,22 +7,9 @@
 
 #include "../../include/vd_hip.h"
 #include "frame_norm.h"
+#include "split16.h"      // split16p (shared with still_rows.hip)
 
 typedef __bf16 bf16_t;
-
-__device__ __forceinline__ void split16p(int prec, float v, uint16_t& hi, uint16_t& lo) {
-    if (prec == VD_PREC_BF16 || prec == VD_PREC_BF16X3) {
-        __bf16 h = (__bf16)v;
-        __bf16 l = (__bf16)(v - (float)h);
-        hi = __builtin_bit_cast(uint16_t, h);
-        lo = __builtin_bit_cast(uint16_t, l);
-    } else {
-        _Float16 h = (_Float16)v;
-        _Float16 l = (_Float16)(v - (float)h);
-        hi = __builtin_bit_cast(uint16_t, h);
-        lo = __builtin_bit_cast(uint16_t, l);
-    }
-}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -220,6 +220,9 @@ class HipBackend:
         self.dither_enabled = True      # (tests switch it off per backend to measure the other two remedies)
         self._dither = 0
         self.resident_rows = True      # (tests switch it off per backend: the per-step conversion of the real clips)
+        # measurement only (tools/bench_still_dm.py, and one test that the two forms feed the first level the same bytes): off, a
+        # batch of stills goes through vds_still_expand + vd_pix2rows -- fp32 clips staged per step -- instead of vdsr_still_rows
+        self.still_rows_fused = True
         self._pool_rows = None
 
     def new_network(self, seed: int):
@@ -381,26 +384,66 @@ class HipBackend:
             if self._pool_rows is None or self._pool_rows[0] != key:
                 self._pool_rows = (key, self.eng_real.pool_rows(pool))
             rows = self._pool_rows[1]
-        G = self._dither
-        if G and segments and all(per % G == 0 for _, per in segments) and sum(n * per for n, per in segments) == index.numel():
-            key = (tuple(segments), G, str(index.device))
-            perm = self._seg_perm.get(key) if hasattr(self, "_seg_perm") else None
-            if perm is None:     # group-major launch order [g][segment][class][q]: the clips of one weight set are consecutive
-                pos, parts = 0, [[] for _ in range(G)]
-                for n, per in segments:
-                    blk = torch.arange(pos, pos + n * per).view(n, per // G, G)
-                    for g in range(G):
-                        parts[g].append(blk[:, :, g].reshape(-1))
-                    pos += n * per
-                perm = torch.cat([torch.cat(pg) for pg in parts]).to(index.device)
-                if not hasattr(self, "_seg_perm"):
-                    self._seg_perm = {}
-                self._seg_perm[key] = perm
+        perm = self._set_permutation(index, segments)
+        if perm is not None:
             f = self.eng_real.forward_sets(pool, index[perm], rows=rows)
             out = torch.empty_like(f)
             out[perm] = f
             return out
         return self.eng_real.forward(pool, index=index, rows=rows)
+
+    def _set_permutation(self, index: torch.Tensor, segments) -> Optional[torch.Tensor]:
+        """The group-major launch order of a class-major ``index`` made of ``segments`` when the real side runs G dither sets
+        that divide every segment's clips per class (clip j of a class -> operand set j mod G), None otherwise."""
+        G = self._dither
+        if not (G and segments and all(per % G == 0 for _, per in segments) and sum(n * per for n, per in segments) == index.numel()):
+            return None
+        key = (tuple(segments), G, str(index.device))
+        perm = self._seg_perm.get(key) if hasattr(self, "_seg_perm") else None
+        if perm is None:     # group-major launch order [g][segment][class][q]: the clips of one weight set are consecutive
+            pos, parts = 0, [[] for _ in range(G)]
+            for n, per in segments:
+                blk = torch.arange(pos, pos + n * per).view(n, per // G, G)
+                for g in range(G):
+                    parts[g].append(blk[:, :, g].reshape(-1))
+                pos += n * per
+            perm = torch.cat([torch.cat(pg) for pg in parts]).to(index.device)
+            if not hasattr(self, "_seg_perm"):
+                self._seg_perm = {}
+            self._seg_perm[key] = perm
+        return perm
+
+    def embed_stills(self, pool: torch.Tensor, index: torch.Tensor, per_class: int = 0) -> torch.Tensor:
+        """``embed_pool`` for a pool of STILLS (N,3,H,W): features of the still clips pool[index] repeated over the frames.  A
+        still pool has no resident rows -- the batch's first-level rows are written per step straight from the images
+        (vdsr_still_rows) -- and the dither sets are dealt as ``embed_pool`` deals them."""
+        segs = [(index.numel() // per_class, per_class)] if (per_class and index.numel() % per_class == 0) else None
+        return self.embed_stills_segments(pool, index, segs)
+
+    def embed_stills_segments(self, pool: torch.Tensor, index: torch.Tensor, segments) -> torch.Tensor:
+        """``embed_pool_segments`` for a pool of stills.  ``index`` is a device table the trainer's class ranges bound."""
+        perm = self._set_permutation(index, segments)
+        eng = self.eng_real
+        if not self.still_rows_fused:      # the two-launch composition: fp32 clips of the batch, then the clips' own path
+            if perm is not None:
+                clips = self.hip.still_expand(pool, index[perm], self.geo.frames, checked=True)
+                f = eng.forward_sets(clips, torch.arange(clips.shape[0], device=clips.device))
+            else:
+                return eng.forward(self.hip.still_expand(pool, index, self.geo.frames, checked=True))
+        elif perm is not None:
+            f = eng.forward_sets(None, index[perm], stills=pool)
+        else:
+            return eng.forward(None, index=index, stills=pool)
+        out = torch.empty_like(f)
+        out[perm] = f
+        return out
+
+    def still_expand(self, images, index, T: int):
+        """Still clips of the rows ``index`` (None: all) on the current stream; a device ``index`` is passed as it is."""
+        return self.hip.still_expand(images, index, T, checked=True)
+
+    def still_reduce(self, g_clips):
+        return self.hip.still_reduce(g_clips.contiguous())
 
     def embed_keep(self, x: torch.Tensor):
         return self.eng_syn.forward(x, keep=True)
@@ -696,10 +739,7 @@ class DMTrainer:
         f_real = self._exchange(self._real_features(idx_t))
         f_syn, handle = be.embed_syn(self.image_syn, weights) if hasattr(be, "embed_syn") else be.embed_keep(self.image_syn)
         loss_c, g_syn = be.dm_loss(f_real, f_syn, ncls)
-        grad = be.embed_backward(handle, g_syn)
-        if self.exchange == "allreduce":
-            grad = self._allreduce_pixel_grad(grad)
-        be.sgd(self.image_syn, self.buf, grad, self.lr_img, self.momentum, first=(self.steps_done == 0))
+        self._apply_pixel_grad(be.embed_backward(handle, g_syn), self.steps_done == 0)
         self.steps_done += 1
         return loss_c.sum()
 
@@ -717,10 +757,23 @@ class DMTrainer:
         be = self.be
         if after is not None:
             torch.cuda.current_stream(self.image_syn.device).wait_event(after)
-        grad = be.embed_backward(handle, g_syn)
+        self._apply_pixel_grad(be.embed_backward(handle, g_syn), first)
+
+    # -- what differs between clips and still images (StillDMTrainer) ------------------------------------------------------
+    def _apply_pixel_grad(self, grad: torch.Tensor, first: bool) -> None:
+        """One optimiser step on the synthetic pixels with the gradient ``grad`` of all owned clips (on the current stream)."""
         if self.exchange == "allreduce":
             grad = self._allreduce_pixel_grad(grad)
-        be.sgd(self.image_syn, self.buf, grad, self.lr_img, self.momentum, first=first)
+        self.be.sgd(self.image_syn, self.buf, grad, self.lr_img, self.momentum, first=first)
+
+    def _embed_real(self, idx_t: torch.Tensor, segments=None) -> torch.Tensor:
+        """Features of the pool rows ``idx_t``: ``segments`` (hybrid) as ``embed_pool_segments`` takes them."""
+        be = self.be
+        if segments is not None:
+            return be.embed_pool_segments(self.pool.clips, idx_t, segments) if hasattr(be, "embed_pool_segments") else \
+                be.embed_pool(self.pool.clips, idx_t)
+        return be.embed_pool(self.pool.clips, idx_t, self._per_class()) if hasattr(be, "set_real_weights") else \
+            be.embed_pool(self.pool.clips, idx_t)
 
     def _real_features(self, idx_t: torch.Tensor) -> torch.Tensor:
         """This rank's contribution to the real side: all clips' features of the owned classes (class sharding), or --
@@ -730,18 +783,14 @@ class DMTrainer:
         be = self.be
         if self.shard == "hybrid":
             nb, ns, per = len(self.block), len(self.split), self.batch_real // self.world
-            if hasattr(be, "embed_pool_segments"):
-                f = be.embed_pool_segments(self.pool.clips, idx_t, [(n, p) for n, p in ((nb, self.batch_real), (ns, per)) if n])
-            else:
-                f = be.embed_pool(self.pool.clips, idx_t)
+            f = self._embed_real(idx_t, [(n, p) for n, p in ((nb, self.batch_real), (ns, per)) if n])
             parts = []
             if nb:
                 parts.append(be.group_sum(f[:nb * self.batch_real].contiguous(), nb, self.batch_real, 1.0 / self.batch_real))
             if ns:
                 parts.append(be.group_sum(f[nb * self.batch_real:].contiguous(), ns, per, 1.0 / self.batch_real))
             return torch.cat(parts, 0)
-        f = be.embed_pool(self.pool.clips, idx_t, self._per_class()) if hasattr(be, "set_real_weights") else \
-            be.embed_pool(self.pool.clips, idx_t)
+        f = self._embed_real(idx_t)
         if self.shard != "batch":
             return f
         return be.group_sum(f, self.num_classes, self.batch_real // self.world, 1.0 / self.batch_real)
@@ -1318,6 +1367,82 @@ class StillGMTrainer(GMTrainer):
         import types
         return DMTrainer.gather_syn(types.SimpleNamespace(world=self.world, num_classes=self.num_classes, ipc=self.spc,
                                                           image_syn=self.static))
+
+
+class StillDMTrainer(DMTrainer):
+    """Distribution matching on STILL clips: the static-learning stage of the static + dynamic method on the DM loop
+    (``StillGMTrainer`` is the same stage on gradient matching).  The memories are ``static`` (n_owned*spc, 3, H, W) images
+    with a momentum buffer of that shape; ``pool.clips`` holds stills (N, 3, H, W).
+
+    Real side: the batch is an index into the stills; the HIP backend writes the first level's operand rows straight from the
+    images (``embed_stills*``: vdsr_still_rows, no fp32 clips), a backend without that embeds ``expand(pool[idx])``.  Synthetic
+    side, all on the synthetic-clip stream: ``image_syn = still_expand(static)`` goes through ``embed_syn``; the clip gradient
+    is summed over T in ascending t (``still_reduce``), SGD with momentum steps ``static``, and ``image_syn`` is expanded
+    again for the next step -- inside ``_apply_pixel_grad``, so ``step(it, overlap=True)`` and the deferred backward keep
+    their order: SGD(i) and the expansion precede the forward of step i + 1.
+
+    Pooling ties: the real side has no gradient, so which of two equal frames its temporal max-pool picks changes nothing;
+    the synthetic side is ``StillGMTrainer``'s argument (a tie moves gradient between frames of one clip, the sum over T is
+    the same)."""
+
+    def __init__(self, backend, pool: RealPool, geo: P.NetGeometry, num_classes: int, spc: int, batch_real: int, lr_img: float,
+                 momentum: float = 0.5, rank: int = 0, world: int = 1, static: Optional[torch.Tensor] = None,
+                 shard: str = "class", exchange: str = "owner"):
+        if exchange != "owner":
+            raise ValueError("StillDMTrainer: exchange=%r is a benchmark leg of the clip trainer; the still trainer is owner-computes" % (exchange,))
+        stills = pool.clips
+        if stills.dim() != 4 or tuple(stills.shape[1:]) != (3, geo.height, geo.width):
+            raise ValueError("StillDMTrainer: a pool of stills (N, 3, %d, %d), not %s" % (geo.height, geo.width, tuple(stills.shape)))
+        self.geo, self.spc = geo, int(spc)
+        # the base class decides the sharding (``shard``, ``classes``, ``block`` / ``split``) on an empty memory; the images, their
+        # momentum and the clips follow below, once the classes this rank owns and reads are known
+        super().__init__(backend, pool, num_classes, spc, batch_real, lr_img, momentum=momentum, rank=rank, world=world,
+                         image_syn=stills[:0], shard=shard, exchange=exchange)
+        owned = self.classes
+        read = list(range(num_classes)) if self.shard == "batch" else (self.block + self.split if self.shard == "hybrid" else owned)
+        for c in read:          # (every index sample_real_indices draws lies in the pool: the kernel does not check)
+            if pool.offsets[c] < 0 or pool.offsets[c] + pool.counts[c] > stills.shape[0]:
+                raise ValueError("StillDMTrainer: class %d occupies rows %d..%d of a pool of %d stills"
+                                 % (c, pool.offsets[c], pool.offsets[c] + pool.counts[c], stills.shape[0]))
+        if static is None:          # --init real: the first spc stills of each owned class
+            idx = np.concatenate([pool.offsets[c] + np.arange(spc) % pool.counts[c] for c in owned]) if owned \
+                else np.zeros(0, dtype=np.int64)
+            static = stills[torch.as_tensor(idx, device=stills.device, dtype=torch.int64)].clone()
+        if tuple(static.shape) != (len(owned) * spc, 3, geo.height, geo.width):
+            raise ValueError("StillDMTrainer: static %s for %d owned classes x spc %d" % (tuple(static.shape), len(owned), spc))
+        self.static = static.contiguous()
+        self.buf = torch.zeros_like(self.static)          # momentum of the IMAGES
+        self.image_syn = self._expand_static()
+
+    def _expand_static(self) -> torch.Tensor:
+        """``still_expand(static)`` as a fresh tensor that the synthetic-clip stream may read."""
+        x = still_expand(self.be, self.static, None, self.geo.frames)
+        if getattr(self.be, "two_streams", False):
+            x.record_stream(self.be.s_syn)
+        return x
+
+    def _embed_real(self, idx_t: torch.Tensor, segments=None) -> torch.Tensor:
+        be = self.be
+        if hasattr(be, "embed_stills"):
+            if segments is not None:
+                return be.embed_stills_segments(self.pool.clips, idx_t, segments)
+            return be.embed_stills(self.pool.clips, idx_t, self._per_class())
+        clips = still_expand(be, self.pool.clips, idx_t, self.geo.frames)
+        return be.embed_pool(clips, torch.arange(clips.shape[0], device=clips.device))
+
+    def _apply_pixel_grad(self, grad: torch.Tensor, first: bool) -> None:
+        be = self.be
+        be.sgd(self.static, self.buf, still_reduce(be, grad), self.lr_img, self.momentum, first=first)
+        self.image_syn = self._expand_static()          # the clips of the next step
+
+    def gather_static(self) -> torch.Tensor:
+        """All ranks' images in class order on every rank: row ``c*spc + j`` (``static_*.pt``), after the steps in flight."""
+        self.sync()
+        if not collectives_on(self.world):
+            return self.static
+        import types
+        return DMTrainer.gather_syn(types.SimpleNamespace(world=self.world, num_classes=self.num_classes, ipc=self.spc,
+                                                          image_syn=self.static, owned_classes=self.owned_classes))
 
 
 # ------------------------------------------------------------------------------------------------

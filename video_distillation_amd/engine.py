@@ -496,16 +496,22 @@ class EmbedEngine:
         return rows
 
     def forward(self, x: torch.Tensor, keep: bool = False, index: Optional[torch.Tensor] = None,
-                rows: Optional[torch.Tensor] = None, group: Optional[int] = None):
+                rows: Optional[torch.Tensor] = None, group: Optional[int] = None, stills: Optional[torch.Tensor] = None):
         """x (B,T,3,H,W) fp32 on the device -> features (B, num_feat) fp32.  With ``keep`` the
         pooling arg-max of every layer is retained and returned as a handle for ``backward``
         (several forwards may be outstanding before their backwards, as in the reference's
-        per-class loop, distill_baseline.py:344-354).  ``group``: multiply by dithered operand set g of ``set_weights(dither=G)``."""
+        per-class loop, distill_baseline.py:344-354).  ``group``: multiply by dithered operand set g of ``set_weights(dither=G)``.
+        ``stills`` (N,3,H,W) with ``index`` (``x`` None): the batch is the still clips stills[index[b]] repeated over the frames;
+        their first-level rows are written straight from the images (vdsr_still_rows), everything after is the clips' path."""
         assert self._weights is not None, "set_weights() first"
         assert group is None or 0 <= group < getattr(self, "_dither", 0), "set_weights(dither=G) first"
         g = self.geo
-        assert x.dim() == 5 and tuple(x.shape[1:]) == (g.frames, g.channel, g.height, g.width), x.shape
-        x = x.detach().to(torch.float32).contiguous()
+        if stills is not None:
+            assert x is None and rows is None and index is not None, "stills: a pool of images and an index, nothing else"
+            stills = self._check_stills(stills)
+        else:
+            assert x.dim() == 5 and tuple(x.shape[1:]) == (g.frames, g.channel, g.height, g.width), x.shape
+            x = x.detach().to(torch.float32).contiguous()
         B = x.shape[0] if index is None else int(index.numel())
         if index is not None:   # batch clip b = x[index[b]] (gather fused into the slot conversion)
             index = index.to(self.device, torch.int64).contiguous()
@@ -522,9 +528,12 @@ class EmbedEngine:
             else:
                 slots0 = self.rows_buf(nb)
                 lo = slots0[1] if self.planes == 2 else None
-                xin = x[c0:] if index is None else x
-                hip.run("vd_pix2rows", hip.ptr(xin), hip.ptr(None if index is None else index[c0:]), nb, g.frames, g.height,
-                        g.width, hip.ptr(slots0[0]), hip.ptr(lo), self.prec, st)
+                if stills is not None:
+                    self._still_rows(stills, index[c0:], nb, slots0, lo, st)
+                else:
+                    xin = x[c0:] if index is None else x
+                    hip.run("vd_pix2rows", hip.ptr(xin), hip.ptr(None if index is None else index[c0:]), nb, g.frames, g.height,
+                            g.width, hip.ptr(slots0[0]), hip.ptr(lo), self.prec, st)
             n1, n2 = nb * self.per1, nb * self.per2
             hilo = self.fwd2x is not None
             assert not (hilo and keep), "last_hilo engines have no kept-arg-max forward"
@@ -555,11 +564,25 @@ class EmbedEngine:
             return feats, saved
         return feats
 
-    def forward_sets(self, x: torch.Tensor, index: torch.Tensor, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _check_stills(self, stills: torch.Tensor) -> torch.Tensor:
+        g = self.geo
+        assert stills.dim() == 4 and tuple(stills.shape[1:]) == (g.channel, g.height, g.width), stills.shape
+        assert stills.is_cuda and stills.dtype == torch.float32 and stills.is_contiguous(), "stills: contiguous fp32 on the device"
+        return stills.detach()
+
+    def _still_rows(self, stills: torch.Tensor, index: torch.Tensor, nb: int, slots0: torch.Tensor, lo, st) -> None:
+        """The first-level rows of the still clips stills[index[:nb]] into ``slots0`` (and its low plane ``lo``): what
+        vd_pix2rows writes for those clips, without the clips (``index`` is the caller's checked device table)."""
+        g = self.geo
+        hip.run("vdsr_still_rows", hip.ptr(stills), hip.ptr(index), nb, g.frames, g.height, g.width, hip.ptr(slots0[0]), hip.ptr(lo),
+                self.prec, st)
+
+    def forward_sets(self, x: torch.Tensor, index: torch.Tensor, rows: Optional[torch.Tensor] = None,
+                     stills: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Features of x[index] with the clips in G = ``set_weights(dither=G)`` consecutive blocks of len(index) / G, block s
         multiplying by dithered operand set s (single-pass engines): ONE launch per layer, the set picked per box from the clip
         number (VdConvParams.w_set_clips; the first layer's register-resident-B kernel reloads its fragments when a
-        workgroup's walk crosses into the next block)."""
+        workgroup's walk crosses into the next block).  ``stills`` (``x`` None): as in ``forward``."""
         G = getattr(self, "_dither", 0)
         B = int(index.numel())
         assert G >= 2 and B % G == 0 and self.planes == 1, "set_weights(dither=G) on a single-pass engine first"
@@ -572,7 +595,11 @@ class EmbedEngine:
         hilo = self.fwd2x is not None
         act1, act2 = self.act_bufs(B, 2 if hilo else None)
         w = self._weights
-        if rows is None:
+        if stills is not None:
+            assert x is None and rows is None, "stills: a pool of images and an index, nothing else"
+            slots0 = self.rows_buf(B)
+            self._still_rows(self._check_stills(stills), index, B, slots0, None, hip.stream_ptr(self.device))
+        elif rows is None:
             slots0 = self.rows_buf(B)
             hip.run("vd_pix2rows", hip.ptr(x.detach().to(torch.float32).contiguous()), hip.ptr(index), B, g.frames, g.height,
                     g.width, hip.ptr(slots0[0]), hip.ptr(None), self.prec, hip.stream_ptr(self.device))

@@ -19,12 +19,14 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvd_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernels.hip", "program.hip", "planner.cpp", "comm.cpp",
-                                                         "coreset.hip", "clips_sample.hip", "eval_stats.hip", "still.hip", "traj.hip")]
-CSRC_HEADERS = [os.path.join(_HERE, "csrc", "frame_norm.h")]      # included by more than one source: part of every hash below
+                                                         "coreset.hip", "clips_sample.hip", "eval_stats.hip", "still.hip", "still_rows.hip",
+                                                         "traj.hip")]
+CSRC_HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("frame_norm.h", "split16.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
 HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
 HEADER_TRAJ = os.path.join(_HERE, "..", "include", "vd_traj.h")      # the second public header: the vdt_ entry points (csrc/traj.hip)
 HEADER_STILL = os.path.join(_HERE, "..", "include", "vd_still.h")      # the third: the vds_ entry points (csrc/still.hip)
+HEADER_STILLROWS = os.path.join(_HERE, "..", "include", "vd_stillrows.h")      # the fourth: the vdsr_ entry points (csrc/still_rows.hip)
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
@@ -122,7 +124,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER, HEADER_TRAJ, HEADER_STILL, *CSRC_HEADERS)
+        key = _file_hash(src, HEADER, HEADER_TRAJ, HEADER_STILL, HEADER_STILLROWS, *CSRC_HEADERS)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -167,12 +169,12 @@ def library_stamp(path: str = None) -> Optional[str]:
 
 
 def sources_hash() -> str:
-    """sha256 (first 16 hex digits) over the kernel sources and the three ABI headers: what measurement files that are carried from one
+    """sha256 (first 16 hex digits) over the kernel sources and the four ABI headers: what measurement files that are carried from one
     run to the next (profiles/rNN_pmc_traffic.json -> bench.py's ``roofline.traffic``) are stamped with, so that a figure
     measured on other kernels is refused instead of quoted."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER, HEADER_TRAJ, HEADER_STILL] + CSRC_HEADERS:
+    for path in sorted(SOURCES) + [HEADER, HEADER_TRAJ, HEADER_STILL, HEADER_STILLROWS] + CSRC_HEADERS:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -180,13 +182,13 @@ def sources_hash() -> str:
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
 _RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None, "const char*": ctypes.c_char_p}
-_PROTOTYPE = re.compile(r"(int64_t|int|void|const char\s*\*)\s*(vd[ts]?_[a-z0-9_]+)\s*\(([^()]*)\)")
+_PROTOTYPE = re.compile(r"(int64_t|int|void|const char\s*\*)\s*(vd(?:t|s|sr)?_[a-z0-9_]+)\s*\(([^()]*)\)")
 _PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+")
 
 
 def parse_header(text: str, where: str = "include/vd_hip.h") -> dict:
     """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses (names ``vd_*``, ``vdt_*`` for
-    include/vd_traj.h, ``vds_*`` for include/vd_still.h) -> {name: (restype, [argtypes])}.  Anything else -- a type outside the set, a statement that is not wholly
+    include/vd_traj.h, ``vds_*`` for include/vd_still.h, ``vdsr_*`` for include/vd_stillrows.h) -> {name: (restype, [argtypes])}.  Anything else -- a type outside the set, a statement that is not wholly
     a prototype -- is a ``ValueError`` that quotes it; no guesses."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"typedef\s+struct\s*\w*\s*(\{[^{}]*\}\s*)?\w+\s*;", " ", text)
@@ -237,6 +239,17 @@ def signatures_still() -> dict:
     return sigs
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_stillrows() -> dict:
+    """{name: (restype, [argtypes])} of include/vd_stillrows.h, the ``vdsr_`` entry points of the same library."""
+    with open(HEADER_STILLROWS) as f:
+        sigs = parse_header(f.read(), "include/vd_stillrows.h")
+    other = [name for name in sigs if not name.startswith("vdsr_")]
+    if other:
+        raise ValueError("include/vd_stillrows.h declares %s: its entry points carry the prefix vdsr_" % ", ".join(other))
+    return sigs
+
+
 def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
     if name == "EXPORTS":
         return tuple(signatures())
@@ -252,9 +265,10 @@ class _Library(ctypes.CDLL):
 
 def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
     """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h,
-    include/vd_traj.h and include/vd_still.h."""
+    include/vd_traj.h, include/vd_still.h and include/vd_stillrows.h."""
     L = _Library(path)
-    for name, (restype, argtypes) in list(signatures().items()) + list(signatures_ext().items()) + list(signatures_still().items()):
+    for name, (restype, argtypes) in list(signatures().items()) + list(signatures_ext().items()) + list(signatures_still().items()) \
+            + list(signatures_stillrows().items()):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -483,6 +497,47 @@ def still_expand(images: torch.Tensor, index, T: int, checked: bool = False) -> 
     out = torch.empty((n, T, 3, H, W), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         run("vds_still_expand", ptr(images), ptr(idx), n, T, H, W, ptr(out), stream_ptr(dev))
+    return out
+
+
+def still_rows(images: torch.Tensor, index, T: int, prec: int, planes: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``vdsr_still_rows`` on the current stream: the first-level operand rows of the still clips ``images[index]`` repeated over
+    ``T`` frames, -> (planes, n * T * 3 * H * pitch / 8, 8) int16 (``out``: that tensor, or a larger contiguous one of ``planes``
+    planes whose leading part is written), byte for byte ``vd_pix2rows`` of ``still_expand(images, index, T)``.  ``prec`` one of
+    the four codes ``PREC['bf16'] .. PREC['f16x3']`` (0..3); ``planes`` 2 also writes the low plane.  ``index`` is
+    validated as ``still_expand`` validates it: ``ValueError`` for a row outside [0, N) before anything reaches the kernel."""
+    import numpy as np
+    if images.dim() != 4 or int(images.shape[1]) != 3:
+        raise ValueError("still_rows: images: a (n, 3, H, W) tensor, not %s" % (tuple(images.shape),))
+    N, H, W, T = int(images.shape[0]), int(images.shape[2]), int(images.shape[3]), int(T)
+    if T < 1 or H < 1 or W < 1 or prec not in (0, 1, 2, 3) or planes not in (1, 2):
+        raise ValueError("still_rows: T %d, H %d, W %d, prec %r, planes %r" % (T, H, W, prec, planes))
+    host = None
+    if index is not None and not (isinstance(index, torch.Tensor) and index.is_cuda):      # a host table: checked before anything else
+        host = np.ascontiguousarray(np.asarray(index, dtype=np.int64).reshape(-1))
+        if host.size and (int(host.min()) < 0 or int(host.max()) >= N):
+            raise ValueError("still_rows: an index outside [0, %d)" % N)
+    _still_tensor(images, 4, "still_rows: images")
+    dev = images.device
+    if index is None:
+        n, idx = N, None
+    else:
+        if host is None:
+            idx = index.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+            if idx.numel() and bool(((idx < 0) | (idx >= N)).any()):
+                raise ValueError("still_rows: an index outside [0, %d)" % N)
+        else:
+            idx = torch.as_tensor(host).to(dev)
+        n = int(idx.numel())
+    slots = n * T * 3 * H * ((W + 8 + 7) // 8)
+    if out is None:
+        out = torch.empty((planes, slots, 8), dtype=torch.int16, device=dev)
+    elif not (out.is_cuda and out.device == dev and out.dtype == torch.int16 and out.dim() == 3 and out.is_contiguous()
+              and int(out.shape[0]) == planes and int(out.shape[1]) >= slots and int(out.shape[2]) == 8):
+        raise ValueError("still_rows: out is a contiguous (%d, >= %d, 8) int16 tensor on %s" % (planes, slots, dev))
+    with torch.cuda.device(dev):
+        run("vdsr_still_rows", ptr(images), ptr(idx), n, T, H, W, ptr(out[0]), ptr(out[1] if planes == 2 else None), int(prec),
+            stream_ptr(dev))
     return out
 
 

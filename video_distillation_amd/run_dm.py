@@ -11,6 +11,21 @@ whole videos there too, so that evaluation draws its clips per read without deco
 {"clips": (N,T,3,H,W), "labels": (N,), "test_clips", "test_labels"}.  Logging: JSON lines with the reference's wandb keys
 (``Loss``, ``Accuracy/<model>``, ``Max_Accuracy/<model>``, ``Std/<model>``, ``Max_Std/<model>``).  Process setup, log, the
 evaluation round and the project's own flags are shared with the other drivers (``driver.py``).
+
+``--memories static`` learns the static memory of the static + dynamic method by distribution matching on STILL clips
+(``distill.StillDMTrainer``; ``run_dc --memories static`` is the same stage by gradient matching): ``--spc`` still images per
+class, each fed to ConvNet3D repeated over ``--frames`` frames.
+
+    python -m video_distillation_amd.run_dm --memories static --dataset singleUCF50 --data_path D --spc 2
+
+Data as ``run_dc --memories static`` (``run_dc.load_stills``: the ``single*`` datasets, a ``--data_file`` with "images", or
+``synthetic``); ``--init noise`` is drawn in full on the host from ``--seed`` and sliced per rank; ``--ipc`` is not read.
+Evaluation trains on the expanded stills; files are ``static_{it}.pt`` / ``static_best.pt`` = ``{"image": (C*spc,3,H,W)}`` under
+``save_path/Static_DM/{dataset}_spc{spc}_{lr_img}`` -- what ``run_s2d`` / ``run_mtt --memories s2d`` read with ``--path_static``.
+They are written at ``--memories images``' cadence (a new best, or an evaluation iteration that is a multiple of 1000) with ONE
+deviation, which is ``run_dc --memories static``'s: with ``--no_eval``, or data without test images, the evaluation iterations
+that are multiples of 1000 still write their file (``--memories images`` writes nothing then) -- the file is this stage's
+product, and a run that cannot evaluate would otherwise leave none.
 """
 from __future__ import annotations
 
@@ -47,6 +62,11 @@ def build_parser():
     p.add_argument('--pool_per_class', type=int, default=93, help='synthetic data only')
     p.add_argument('--prec_real', type=str, default='f16')
     p.add_argument('--prec_syn', type=str, default='f16x3')
+    p.add_argument('--memories', type=str, default='images', choices=['images', 'static'],
+                   help="images: synthetic clips (images_{it}.pt); static: synthetic still images (static_{it}.pt; unlike images, "
+                        "also written at evaluation iterations that are multiples of 1000 when nothing is evaluated)")
+    p.add_argument('--spc', type=int, default=2, help='--memories static: images per class')
+    p.add_argument('--seed', type=int, default=0, help='--memories static: seed of --init noise')
     driver.add_data_flags(p)
     driver.add_eval_flags(p)
     return p
@@ -81,8 +101,65 @@ def load_data(args, rank, world, geo, device):
     return pool, num_classes, (c_lo, c_hi), driver.file_test_loader(blob)
 
 
-def run(args, backend=None, log=None):
+def run_static(args, backend=None, log=None, shard: str = "class", exchange: str = "owner"):
+    """``--memories static``: the loop of ``run`` on ``distill.StillDMTrainer``."""
     from . import checkpoint, distill, plan, utils
+    from .run_dc import StillTestLoader, load_stills
+    if args.spc < 1:
+        raise ValueError("--spc %d: at least one memory per class" % args.spc)
+    rank, world, device = driver.start(use_cuda=backend is None)
+    geo = plan.NetGeometry(args.frames, args.im_size, args.im_size)
+    pool, num_classes, (c_lo, c_hi), testloader = load_stills(args, rank, world, device)
+    if backend is None:
+        backend = distill.HipBackend(geo, device, prec_real=args.prec_real, prec_syn=args.prec_syn)
+    if testloader is not None:
+        testloader = StillTestLoader(testloader, backend, device, args.frames)
+    static = None
+    if args.init == 'noise':
+        gen = torch.Generator().manual_seed(args.seed)          # drawn in full on the host: every sharding starts from the same state
+        static = torch.randn((num_classes * args.spc, 3, args.im_size, args.im_size), generator=gen)[c_lo * args.spc:c_hi * args.spc].to(device)
+    trainer = distill.StillDMTrainer(backend, pool, geo, num_classes, args.spc, args.batch_real, args.lr_img, momentum=0.5,
+                                     rank=rank, world=world, static=static, shard=shard, exchange=exchange)
+    eval_pool = utils.get_eval_pool(args.eval_mode, args.model, args.model)
+    best_acc = {m: 0.0 for m in eval_pool}; best_std = {m: 0.0 for m in eval_pool}
+    save_dir = os.path.join(args.save_path, "Static_DM", "%s_spc%d_%s" % (args.dataset, args.spc, args.lr_img))
+    log = driver.JsonLog(args.log_file, rank, log)
+    evaluate = not args.no_eval and testloader is not None
+    eval_seed = None
+    if args.eval_ranks == 'all' and evaluate:
+        eval_seed = driver.draw_eval_seed(args.eval_seed, rank, world)
+        log.emit({"eval_ranks": "all", "eval_seed": eval_seed, "world": world})
+    label_syn = torch.arange(num_classes).repeat_interleave(args.spc)
+    eval_its = set(np.arange(0, args.Iteration + 1, args.eval_it).tolist())
+    t0 = time.time()
+    for it in range(args.Iteration + 1):
+        if it in eval_its and (evaluate or it % 1000 == 0):          # (as run_dc: an unevaluated run still leaves its files)
+            syn_all = trainer.gather_syn()          # (collectives: every rank, whoever evaluates or saves)
+            static_all = trainer.gather_static()
+            save_best = False
+            if evaluate:
+                save_best, pooled = driver.evaluate_round(
+                    args, it, syn_all.detach().clone(), label_syn, 'none', args.lr_net, testloader, eval_pool, best_acc, best_std, log,
+                    rank=rank, world=world, device=device, num_classes=num_classes,
+                    pool_seed=None if eval_seed is None else eval_seed + it)
+                for got in pooled:
+                    log.emit({"step": it, "eval_pool": {"train_s": got["times"]["train_s"], "test_pass_s": got["times"]["test_pass_s"],
+                                                        "assignment": got["assignment"]}})
+            if rank == 0 and (save_best or it % 1000 == 0):
+                checkpoint.save_static(save_dir, it, static_all, best=save_best)
+        loss = trainer.global_loss(trainer.step(it, overlap=True))
+        if it % 10 == 0 or it == args.Iteration:
+            trainer.sync()
+            log.emit({"step": it, "Loss": float(loss) / num_classes, "elapsed_s": round(time.time() - t0, 3)})
+    trainer.sync()
+    log.close()
+    return trainer
+
+
+def run(args, backend=None, log=None, shard: str = "class", exchange: str = "owner"):
+    from . import checkpoint, distill, plan, utils
+    if getattr(args, 'memories', 'images') == 'static':
+        return run_static(args, backend, log, shard=shard, exchange=exchange)
     rank, world, device = driver.start(use_cuda=backend is None)
     geo = plan.NetGeometry(args.frames, args.im_size, args.im_size)
     pool, num_classes, (c_lo, c_hi), testloader = load_data(args, rank, world, geo, device)
@@ -93,7 +170,7 @@ def run(args, backend=None, log=None):
         gen = torch.Generator(device=device); gen.manual_seed(4321 + rank)
         image_syn = torch.randn((c_hi - c_lo) * args.ipc, args.frames, 3, args.im_size, args.im_size, device=device, generator=gen)
     trainer = distill.DMTrainer(backend, pool, num_classes, args.ipc, args.batch_real, args.lr_img, momentum=0.5,
-                                rank=rank, world=world, image_syn=image_syn)
+                                rank=rank, world=world, image_syn=image_syn, shard=shard, exchange=exchange)
     eval_pool = utils.get_eval_pool(args.eval_mode, args.model, args.model)
     best_acc = {m: 0.0 for m in eval_pool}; best_std = {m: 0.0 for m in eval_pool}
     save_dir = os.path.join(args.save_path, "Baseline_DM", "%s_ipc%d_%s" % (args.dataset, args.ipc, args.lr_img))

@@ -12,7 +12,7 @@ branch reads.
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m video_distillation_amd.run_mtt ...
 
 ``static.pt``: ``python -m video_distillation_amd.run_dc --memories static --dataset singleUCF50 --data_path D --spc 2`` writes it
-as ``static_best.pt`` / ``static_{it}.pt``.
+as ``static_best.pt`` / ``static_{it}.pt``; ``run_dm --memories static`` with the same flags learns it by distribution matching.
 
 The expert trajectories of ``--buffer_path`` (``replay_buffer_N.pt`` of buffer.py) are served by ``experts.ExpertStore``:
 ``--expert_store host`` keeps one file at a time in pinned host memory, ``resident`` all of them in HBM; ``--buffer_walk all``

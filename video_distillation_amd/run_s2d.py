@@ -7,7 +7,8 @@ distill_s2d_ms.py:312-445, with its flag names and defaults for everything that 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m video_distillation_amd.run_s2d ...
 
 ``static.pt`` is what ``python -m video_distillation_amd.run_dc --memories static --dataset singleUCF50 --data_path D --spc 2``
-writes as ``static_best.pt`` / ``static_{it}.pt`` (or the file the reference offers for download).
+writes as ``static_best.pt`` / ``static_{it}.pt`` -- or ``run_dm --memories static`` with the same flags, the same stage by
+distribution matching -- (or the file the reference offers for download).
 
 Data as ``run_dm`` (``run_dm.load_data``: ``--dataset synthetic``, the reference's frame folders, or ``--data_file f.pt``); process
 setup, log, evaluation round and the project's own flags are ``driver.py``'s.  The static memory comes
