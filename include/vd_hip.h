@@ -572,6 +572,73 @@ int64_t vd_coreset_workspace_bytes(int nclass, int max_count);
 int vd_coreset_select(const float* feats, int dim, const int64_t* offsets, const int32_t* counts, int nclass, int max_count,
                       int ipc, int method, int64_t* out_idx, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The three sections below were headers of their own once (docs/history.md).  Their prefixes vdt_, vds_ and vdsr_ are historical:
+ * they are the exported names and stay; new entry points are vd_*.  The conventions are those at the top of this header; the
+ * argument checks come before any HIP call. */
+
+/* ---- The flat-parameter chain of trajectory matching (MTT; csrc/traj.hip) ---------------------------------------------------
+ * distill_baseline.py:231-283 / distill_s2d_ms.py:238-300 of the reference unroll `syn_steps` student updates over ReparamModule's
+ * flat parameter vector (3.65 M floats at 50 classes) and let autograd walk back through them; distill.MTTTrainer walks back
+ * explicitly.  The entry points below are the elementwise and reducing steps of that walk over the flat vector, one pass each.
+ *
+ * Argument errors: -1 for a null or misaligned pointer (EVERY pointer is 16-byte aligned; only `hv` may be null), -2 for n <= 0.
+ *
+ * Arithmetic.  Every fp32 operation is rounded on its own (no fused multiply-add), so an elementwise output is the float32
+ * evaluation of its formula as written.  Sums are fp64 in a fixed order: a first launch, whose grid depends on n only, leaves one
+ * partial per workgroup in `scratch`; a second launch of ONE workgroup adds the partials in index order and applies the scalar
+ * update.  No atomics and no hand-off between workgroups inside a launch: the same inputs give the same bits. */
+
+/* doubles of `scratch` that vdt_traj_loss and vdt_traj_adjoint need for vectors of n floats (0 for n <= 0) */
+int64_t vdt_traj_scratch_doubles(int64_t n);
+
+/* theta_out[i] = theta[i] - lr_dev[0] * g[i]      (student_params[-1] - syn_lr * grad; out of place: the tape keeps every theta_s) */
+int vdt_traj_step(const float* theta, const float* g, const float* lr_dev, int64_t n, float* theta_out, void* stream);
+
+/* out[0] = dist = sum (theta - target)^2, out[1] = dist0 = sum (theta0 - target)^2 (differences and squares in fp64),
+ * out[2] = dist / dist0 (the grand loss), out[3] = 0;  tbar[i] = (2.0f * (theta[i] - target[i])) / (float)dist0.
+ * Three launches: partials, the fold into `out`, tbar. */
+int vdt_traj_loss(const float* theta, const float* theta0, const float* target, int64_t n, double* scratch, double* out,
+                  float* tbar, void* stream);
+
+/* One reverse step, one pass over the vectors:  tbar[i] += hv[i] in place (hv == NULL: tbar as it is, the first reverse step);
+ * g_lr[0] -= sum (double)tbar[i] * (double)g[i] with the updated tbar;  v[i] = (-(lr_dev[0] * share)) * tbar[i]. */
+int vdt_traj_adjoint(float* tbar, const float* hv, const float* g, const float* lr_dev, float share, int64_t n, double* scratch,
+                     double* g_lr, float* v, void* stream);
+
+/* ---- Still clips (csrc/still.hip; distill.StillGMTrainer, run_dc --memories static) ------------------------------------------
+ * A still clip is one image repeated over T frames: what the reference's `static*` / `single*` datasets hand to ConvNet3D
+ * (distill_utils/dataset.py:626-633).  The images stay in HBM, the clips are built per step, and a clip gradient goes back to
+ * its image as the sum over the frames.
+ *
+ * Contiguous fp32 (int64 for `index`).  Argument errors: -1 for a non-positive T / H / W or a negative n, then 0 for n == 0, then
+ * -1 for a null `images` / `out` / `g_clips` / `g_images`.  16-byte accesses are used where 3*H*W is a multiple of 4 and the
+ * bases are 16-byte aligned, 4-byte accesses otherwise; element offsets are 64-bit.  `index` is a device array the caller has
+ * validated (every entry in [0, N)); it may repeat rows, and may be null for the identity. */
+
+/* out[i][t][c][y][x] = images[index ? index[i] : i][c][y][x], t < T.  images [N][3][H][W], out [n][T][3][H][W]. */
+int vds_still_expand(const float* images, const int64_t* index, int64_t n, int T, int H, int W, float* out, void* stream);
+
+/* g_images[i][c][y][x] = (((g[i][0] + g[i][1]) + g[i][2]) + ... ) + g[i][T-1]  at [c][y][x]: fp32, ascending t, one add per
+ * frame, each rounded on its own.  No atomics: bitwise repeatable.  g_clips [n][T][3][H][W], g_images [n][3][H][W]. */
+int vds_still_reduce(const float* g_clips, int64_t n, int T, int H, int W, float* g_images, void* stream);
+
+/* ---- Still clips as first-level operand rows (csrc/still_rows.hip; distill.StillDMTrainer, run_dm --memories static) ---------
+ * The first conv level reads its input as padded 16-bit pixel rows (vd_pix2rows).  A batch of still clips needs no fp32 clips
+ * on the way there: each 16-byte chunk of a row is built once from the image and stored at the T frame positions.
+ *
+ * Contiguous fp32 `images`, int64 `index`, 16-byte aligned outputs.  Argument errors: -1 for a non-positive T / H / W, a negative
+ * n or a `prec` outside VD_PREC_BF16 .. VD_PREC_F16X3 (0..3), then 0 for n == 0, then -1 for a null `images` / `out_hi`.  16-byte
+ * loads are used where W is a multiple of 4 and `images` is 16-byte aligned, 4-byte loads otherwise; element and byte offsets are
+ * 64-bit.  `index` is as for vds_still_expand. */
+
+/* The first-level operand rows of the n still clips images[index ? index[i] : i] repeated over T frames:
+ *   out[clip i][t*3+c][h][pitch], pitch = ((W + 8 + 7) / 8) * 8 16-bit elements, 3 zero pixels in front, zeros behind
+ * -- byte for byte what vd_pix2rows(x = vds_still_expand(images, index, n, T, H, W), clip_index = null, n, T, H, W, out_hi,
+ * out_lo, prec) writes: out_hi the rn16 values (bf16 for VD_PREC_BF16 / BF16X3, fp16 for VD_PREC_F16 / F16X3), out_lo (may be
+ * null) rn16(v - hi).  images [N][3][H][W]; each output plane holds n * T * 3 * H * pitch elements. */
+int vdsr_still_rows(const float* images, const int64_t* index, int64_t n, int T, int H, int W, void* out_hi, void* out_lo, int prec,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

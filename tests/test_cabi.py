@@ -1,5 +1,5 @@
 """The C-ABI shared library loads and exports every symbol include/vd_hip.h declares, the binding takes every signature from
-that header, and the ctypes struct mirrors have the layout the compiler gives the header's structs
+that header, and the ctypes struct mirrors and hand-mirrored constants have the layout and values the header gives them
 (no compute calls: there is no GPU in the CPU test tier)."""
 import ctypes
 import glob
@@ -10,17 +10,38 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAME = r"vd(?:t|s|sr)?_[a-z0-9_]+"          # vd_*, and the three historical prefixes of the sections at the header's end
+PREFIXED = {"vdt_": ["vdt_traj_adjoint", "vdt_traj_loss", "vdt_traj_scratch_doubles", "vdt_traj_step"],
+            "vds_": ["vds_still_expand", "vds_still_reduce"],
+            "vdsr_": ["vdsr_still_rows"]}
 
 
 def declared_functions():
     text = open(os.path.join(ROOT, "include", "vd_hip.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(?:int|int64_t|void|char\*)\s+(vd_[a-z0-9_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(?:int|int64_t|void|char\*)\s+(%s)\s*\(" % NAME, text)))
 
 
 def test_header_and_binding_agree():
     from video_distillation_amd import hip
     assert declared_functions() == sorted(hip.EXPORTS)
+
+
+def test_the_three_prefixed_sections_are_declared_bound_and_exported():
+    """The exact name set of each historical prefix, in the header, in the binding and in the library; the other 86 are vd_*."""
+    from video_distillation_amd import hip
+    for prefix, names in PREFIXED.items():
+        assert [n for n in declared_functions() if n.startswith(prefix)] == names == sorted(n for n in hip.EXPORTS if n.startswith(prefix))
+    assert len([n for n in hip.EXPORTS if n.startswith("vd_")]) == 86 == len(hip.EXPORTS) - 7
+    if not os.path.exists(hip.LIB_PATH):
+        hip.build()
+    lib = hip.bind(hip.LIB_PATH)
+    for name in sum(PREFIXED.values(), []):
+        assert hasattr(lib, name), name
+    assert lib.vd_abi_version() == 5
+    names = [os.path.basename(s) for s in hip.SOURCES]
+    assert names[-1] == "traj.hip" and names[:2] == ["conv_mfma.hip", "aux_kernels.hip"]
+    assert "still.hip" in names and "still_rows.hip" in names
 
 
 def test_library_exports_every_declared_symbol():
@@ -85,13 +106,13 @@ def _prototype_text():
 
 def test_every_prototype_of_the_header_is_parsed():
     from video_distillation_amd import hip
-    assert len(hip.signatures()) == len(re.findall(r"vd_[a-z0-9_]+\(", _prototype_text())) == 86
+    assert len(hip.signatures()) == len(re.findall(r"\b%s\(" % NAME, _prototype_text())) == 93
     assert hip.EXPORTS == tuple(hip.signatures())
     defined = []
     csrc = os.path.join(ROOT, "video_distillation_amd", "csrc")
     for path in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")):
-        defined += re.findall(r'extern\s+"C"\s+(?:const\s+)?\w+\s*\*?\s*(vd_[a-z0-9_]+)\s*\(', open(path).read())
-    assert sorted(defined) == sorted(hip.signatures())
+        defined += re.findall(r'extern\s+"C"\s+(?:const\s+)?\w+\s*\*?\s*(%s)\s*\(' % NAME, open(path).read())
+    assert sorted(defined) == sorted(hip.signatures()) and len(defined) == 93
 
 
 def test_signatures_pinned_by_hand():
@@ -116,6 +137,27 @@ def test_signatures_pinned_by_hand():
         assert fn.restype is restype and list(fn.argtypes) == argtypes, name
 
 
+def test_signatures_of_the_prefixed_entry_points_pinned_by_hand():
+    from video_distillation_amd import hip
+    i, q, f, p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+    pinned = {
+        "vdt_traj_scratch_doubles": (q, [q]),
+        "vdt_traj_step": (i, [p, p, p, q, p, p]),
+        "vdt_traj_loss": (i, [p, p, p, q, p, p, p, p]),
+        "vdt_traj_adjoint": (i, [p, p, p, p, f, q, p, p, p, p]),
+        "vds_still_expand": (i, [p, p, q, i, i, i, p, p]),
+        "vds_still_reduce": (i, [p, q, i, i, i, p, p]),
+        "vdsr_still_rows": (i, [p, p, q, i, i, i, p, p, i, p]),
+    }
+    assert {name: sig for name, sig in hip.signatures().items() if not name.startswith("vd_")} == pinned          # all seven
+    lib = hip.lib()
+    for name, (restype, argtypes) in pinned.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    with pytest.raises(TypeError):
+        lib.vdt_traj_step(None, None, None, 4, None)           # a wrong count is an exception before the call
+
+
 @pytest.mark.parametrize("text,quoted", [
     ("int vd_a(int n);\nint vd_b(float* x, unsigned long n, void* stream);\n", "unsigned long n"),
     ("int vd_a(int n);\nint vd_b(void (*done)(int), void* stream);\n", "void (*done)(int)"),
@@ -129,6 +171,15 @@ def test_the_parser_refuses_what_it_does_not_know(text, quoted):
     with pytest.raises(ValueError) as e:
         hip.parse_header("/* a header */\n#include <stdint.h>\n" + text)
     assert quoted in str(e.value)
+
+
+@pytest.mark.parametrize("prefix", ["vdt_", "vds_", "vdsr_"])
+def test_the_parser_names_the_header_it_refuses(prefix):
+    from video_distillation_amd import hip
+    with pytest.raises(ValueError, match=r"^include/vd_hip\.h: .*unsigned n"):
+        hip.parse_header("int %sa(unsigned n);" % prefix)
+    with pytest.raises(ValueError, match=r"^some/other\.h: "):
+        hip.parse_header("int %sa(unsigned n);" % prefix, "some/other.h")
 
 
 def test_plain_python_ints_travel_in_the_declared_width():
@@ -227,3 +278,36 @@ def test_library_carries_the_hash_of_its_sources_and_a_stale_one_is_refused(tmp_
     monkeypatch.setattr(hip, "build", no_compiler)
     with pytest.raises(RuntimeError, match="built from other sources"):
         hip.lib()
+
+
+def test_sources_hash_covers_the_header_the_kernel_files_and_the_shared_headers(tmp_path, monkeypatch):
+    from video_distillation_amd import hip
+    want = hip.sources_hash()
+    other = tmp_path / "vd_hip.h"
+    other.write_text(open(hip.HEADER).read() + "\n/* touched */\n")
+    monkeypatch.setattr(hip, "HEADER", str(other))
+    assert hip.sources_hash() != want
+    monkeypatch.undo()
+    assert hip.sources_hash() == want
+    for name, attr in (("still.hip", "SOURCES"), ("still_rows.hip", "SOURCES"), ("split16.h", "CSRC_HEADERS")):
+        paths = getattr(hip, attr)
+        src = tmp_path / name
+        src.write_text(open([s for s in paths if s.endswith("/" + name)][0]).read() + "\n// touched\n")
+        monkeypatch.setattr(hip, attr, [str(src) if s.endswith("/" + name) else s for s in paths])
+        assert hip.sources_hash() != want, name
+        monkeypatch.undo()
+
+
+def test_constants_mirrored_by_hand_equal_the_header_s_defines():
+    """hip.py reads no file on import, so it restates a few of the header's ``#define``s; each is compared here."""
+    import inspect
+    from video_distillation_amd import hip
+    text = re.sub(r"/\*.*?\*/", "", open(hip.HEADER).read(), flags=re.S)
+    defines = {name: int(value) for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(VD_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
+    assert hip.PREC == {name[len("VD_PREC_"):].lower(): v for name, v in defines.items() if name.startswith("VD_PREC_")}
+    assert len(hip.PREC) == 5 and sorted(hip.PREC.values()) == [0, 1, 2, 3, 4]
+    assert hip.F16X3_WSHIFT == defines["VD_F16X3_WSHIFT"]
+    assert hip.VD_PACK_MAX == defines["VD_PACK_MAX"] and hip.VD_MATCH_MAX_SEG == defines["VD_MATCH_MAX_SEG"]
+    assert hip.CORESET_METHOD == {"herding": defines["VD_CORESET_HERDING"], "k-center": defines["VD_CORESET_KCENTER"]}
+    assert defines["VD_ABI_VERSION"] == 5
+    assert "vd_abi_version() != %d:" % defines["VD_ABI_VERSION"] in inspect.getsource(hip.lib)

@@ -1,9 +1,7 @@
-"""Still clips without a GPU: the third public header (include/vd_still.h) and its binding, the argument checks of the two ``vds_``
-entry points, one ``distill.StillGMTrainer`` step on the oracle ops against plain autograd through ``img.unsqueeze(1).expand``,
+"""Still clips without a GPU: the argument checks of the two ``vds_`` entry points (their declarations and binding:
+tests/test_cabi.py), one ``distill.StillGMTrainer`` step on the oracle ops against plain autograd through ``img.unsqueeze(1).expand``,
 and ``GMTrainer``'s two hooks, whose default bodies are the expressions they replaced."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,41 +11,11 @@ from oracle import ref_cpu as R
 from tests.cpu_backend import OracleBackend, OracleGMOps
 from video_distillation_amd import distill, hip, plan
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ["vds_still_expand", "vds_still_reduce"]
 C, SPC, T, HW = 2, 1, 8, 64
 LR = 0.1
 
 
-# ---- header and ABI -------------------------------------------------------------------------------------------------------
-
-def test_third_header_parses_and_the_library_exports_it():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vd_still.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\bint\s+(vds_[a-z0-9_]+)\s*\(", text))) == NAMES == sorted(hip.signatures_still())
-    assert not set(hip.signatures()) & set(NAMES) and not set(hip.signatures_ext()) & set(NAMES)
-    i, q, p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
-    assert hip.signatures_still() == {"vds_still_expand": (i, [p, p, q, i, i, i, p, p]), "vds_still_reduce": (i, [p, q, i, i, i, p, p])}
-    lib = hip.lib()
-    for name, (restype, argtypes) in hip.signatures_still().items():
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
-    assert any(s.endswith("still.hip") for s in hip.SOURCES)
-    with pytest.raises(ValueError, match="vd_still.h"):
-        hip.parse_header("int vds_a(unsigned n);", "include/vd_still.h")
-
-
-def test_sources_hash_covers_the_third_header_and_the_kernel_file(tmp_path, monkeypatch):
-    want = hip.sources_hash()
-    other = tmp_path / "vd_still.h"
-    other.write_text(open(hip.HEADER_STILL).read() + "\n/* touched */\n")
-    monkeypatch.setattr(hip, "HEADER_STILL", str(other))
-    assert hip.sources_hash() != want
-    monkeypatch.undo()
-    src = tmp_path / "still.hip"
-    src.write_text(open([s for s in hip.SOURCES if s.endswith("still.hip")][0]).read() + "\n// touched\n")
-    monkeypatch.setattr(hip, "SOURCES", [str(src) if s.endswith("still.hip") else s for s in hip.SOURCES])
-    assert hip.sources_hash() != want
-
+# ---- ABI --------------------------------------------------------------------------------------------------------------
 
 def test_argument_errors_come_back_as_codes_before_any_device_call():
     """-1 for a non-positive T / H / W or a negative n, 0 for n == 0, -1 for a null pointer with work to do -- with no GPU in

@@ -1,10 +1,8 @@
-"""Distribution matching on still clips without a GPU: the fourth public header (include/vd_stillrows.h) and its binding, the
-argument checks of ``vdsr_still_rows``, three ``distill.StillDMTrainer`` steps on ``tests.cpu_backend.OracleBackend`` against a
+"""Distribution matching on still clips without a GPU: the argument checks of ``vdsr_still_rows`` (its declaration and binding:
+tests/test_cabi.py), three ``distill.StillDMTrainer`` steps on ``tests.cpu_backend.OracleBackend`` against a
 hand-written loop that differentiates the oracle's DM loss through ``img.unsqueeze(1).expand`` by autograd, ``DMTrainer``'s two
 hooks, class and batch sharding over two gloo ranks, and ``run_dm --memories static`` on the oracle backend."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,52 +12,12 @@ from oracle import ref_cpu as R
 from tests.cpu_backend import OracleBackend
 from video_distillation_amd import checkpoint, distill, hip, plan, run_dm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C, SPC, T, HW, PER, BATCH = 2, 2, 8, 64, 12, 8
 LR, MU, STEPS = 0.1, 0.5, 3
 SEED = 4343
 
 
-# ---- header and ABI -------------------------------------------------------------------------------------------------------
-
-def test_fourth_header_parses_and_the_library_exports_it():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vd_stillrows.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\bint\s+(vdsr_[a-z0-9_]+)\s*\(", text))) == ["vdsr_still_rows"] == sorted(hip.signatures_stillrows())
-    i, q, p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
-    assert hip.signatures_stillrows() == {"vdsr_still_rows": (i, [p, p, q, i, i, i, p, p, i, p])}
-    fn = hip.lib().vdsr_still_rows
-    assert fn.restype is i and list(fn.argtypes) == [p, p, q, i, i, i, p, p, i, p]
-    with pytest.raises(ValueError, match="vd_stillrows.h"):
-        hip.parse_header("int vdsr_a(unsigned n);", "include/vd_stillrows.h")
-
-
-def test_the_first_three_headers_are_as_they_were():
-    assert len(hip.signatures()) == 86
-    assert sorted(hip.signatures_still()) == ["vds_still_expand", "vds_still_reduce"]
-    text = re.sub(r"/\*.*?\*/", "", open(hip.HEADER_TRAJ).read(), flags=re.S)
-    assert sorted(hip.signatures_ext()) == sorted(set(re.findall(r"\b(vdt_[a-z0-9_]+)\s*\(", text)))
-    for sigs in (hip.signatures(), hip.signatures_ext(), hip.signatures_still()):
-        assert not [name for name in sigs if name.startswith("vdsr_")]
-    names = [os.path.basename(s) for s in hip.SOURCES]
-    assert names[-1] == "traj.hip" and names[:2] == ["conv_mfma.hip", "aux_kernels.hip"] and "still_rows.hip" in names
-
-
-def test_sources_hash_covers_the_fourth_header_and_the_kernel_file(tmp_path, monkeypatch):
-    want = hip.sources_hash()
-    other = tmp_path / "vd_stillrows.h"
-    other.write_text(open(hip.HEADER_STILLROWS).read() + "\n/* touched */\n")
-    monkeypatch.setattr(hip, "HEADER_STILLROWS", str(other))
-    assert hip.sources_hash() != want
-    monkeypatch.undo()
-    assert hip.sources_hash() == want
-    for name, attr in (("still_rows.hip", "SOURCES"), ("split16.h", "CSRC_HEADERS")):
-        paths = getattr(hip, attr)
-        src = tmp_path / name
-        src.write_text(open([s for s in paths if s.endswith(name)][0]).read() + "\n// touched\n")
-        monkeypatch.setattr(hip, attr, [str(src) if s.endswith(name) else s for s in paths])
-        assert hip.sources_hash() != want, name
-        monkeypatch.undo()
-
+# ---- ABI --------------------------------------------------------------------------------------------------------------
 
 def test_argument_errors_come_back_as_codes_before_any_device_call():
     """-1 for a non-positive T / H / W, a negative n or a prec outside 0..3; then 0 for n == 0; then -1 for a null ``images`` /

@@ -1,11 +1,8 @@
-"""The second public header (include/vd_traj.h) and its binding, the argument checks of the ``vdt_`` entry points without a
-GPU, the numpy oracle of the chain against plain fp64, ``experts.ExpertStore`` on the CPU (rows, walks, refusals) and
-``MTTTrainer.step`` fed from a ``FlatTrajectory`` against the list form (oracle ops; C = 3, 64x64x8)."""
-import ctypes
+"""The argument checks of the ``vdt_`` entry points without a GPU (their declarations and binding: tests/test_cabi.py), the
+numpy oracle of the chain against plain fp64, ``experts.ExpertStore`` on the CPU (rows, walks, refusals) and ``MTTTrainer.step`` fed from a ``FlatTrajectory`` against the list form (oracle ops; C = 3, 64x64x8)."""
 import math
 import os
 import random
-import re
 
 import numpy as np
 import pytest
@@ -14,54 +11,10 @@ import torch
 from tests import traj_oracle as O
 from video_distillation_amd import checkpoint, distill, experts, hip
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C = 3
-NAMES = ["vdt_traj_adjoint", "vdt_traj_loss", "vdt_traj_scratch_doubles", "vdt_traj_step"]
 
 
-# ---- header and ABI -------------------------------------------------------------------------------------------------------
-
-def test_second_header_parses_and_the_library_exports_it():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vd_traj.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(?:int|int64_t)\s+(vdt_[a-z0-9_]+)\s*\(", text)))
-    assert declared == NAMES == sorted(hip.signatures_ext())
-    assert len(hip.signatures()) == 86 and not set(hip.signatures()) & set(NAMES)          # the first header is as it was
-    assert hip.EXPORTS == tuple(hip.signatures())
-    if not os.path.exists(hip.LIB_PATH):
-        hip.build()
-    lib = hip.bind(hip.LIB_PATH)
-    for name in NAMES:
-        assert hasattr(lib, name), name
-    assert lib.vd_abi_version() == 5
-    assert hip.SOURCES[-1].endswith("traj.hip") and [os.path.basename(s) for s in hip.SOURCES[:2]] == ["conv_mfma.hip", "aux_kernels.hip"]
-
-
-def test_signatures_of_the_chain_pinned_by_hand():
-    i, q, f, p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
-    pinned = {
-        "vdt_traj_scratch_doubles": (q, [q]),
-        "vdt_traj_step": (i, [p, p, p, q, p, p]),
-        "vdt_traj_loss": (i, [p, p, p, q, p, p, p, p]),
-        "vdt_traj_adjoint": (i, [p, p, p, p, f, q, p, p, p, p]),
-    }
-    assert hip.signatures_ext() == pinned
-    lib = hip.lib()
-    for name, (restype, argtypes) in pinned.items():
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
-    with pytest.raises(TypeError):
-        lib.vdt_traj_step(None, None, None, 4, None)           # a wrong count is an exception before the call
-    with pytest.raises(ValueError, match="vd_traj.h"):
-        hip.parse_header("int vdt_a(unsigned n);", "include/vd_traj.h")
-
-
-def test_sources_hash_covers_the_second_header(tmp_path, monkeypatch):
-    want = hip.sources_hash()
-    other = tmp_path / "vd_traj.h"
-    other.write_text(open(hip.HEADER_TRAJ).read() + "\n/* touched */\n")
-    monkeypatch.setattr(hip, "HEADER_TRAJ", str(other))
-    assert hip.sources_hash() != want
-
+# ---- ABI --------------------------------------------------------------------------------------------------------------
 
 def test_argument_errors_come_back_as_codes_before_any_device_call():
     """Null, misaligned (4 bytes off) and n <= 0: -1 / -2 as in include/vd_hip.h, with no GPU in the machine.  The addresses

@@ -1,4 +1,4 @@
-"""Numpy restatements of the flat-parameter chain of include/vd_traj.h (TEST INFRASTRUCTURE ONLY): the elementwise parts in
+"""Numpy restatements of the flat-parameter chain of include/vd_hip.h (``vdt_``; TEST INFRASTRUCTURE ONLY): the elementwise parts in
 float32 with every operation rounded on its own -- what the kernels promise bit for bit --, the sums with ``math.fsum`` over the
 fp64 terms the kernels form (fp64 difference then fp64 square; the fp64 product of two float32 values, which is exact)."""
 import math

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vd_still.h"
+#include "../../include/vd_hip.h"
 
 namespace {
 

@@ -17,7 +17,6 @@
 #include <stdint.h>
 
 #include "../../include/vd_hip.h"
-#include "../../include/vd_stillrows.h"
 #include "split16.h"
 
 namespace {

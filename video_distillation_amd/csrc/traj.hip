@@ -1,4 +1,4 @@
-// The flat-parameter chain of trajectory matching (include/vd_traj.h): the student update, the normalised distance with its
+// The flat-parameter chain of trajectory matching (include/vd_hip.h): the student update, the normalised distance with its
 // adjoint seed, and one reverse step, each ONE pass over the 3.65 M-float parameter vector instead of a string of elementwise and
 // reduction launches with a temporary apiece.
 //
@@ -17,7 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vd_traj.h"
+#include "../../include/vd_hip.h"
 
 namespace {
 

@@ -1466,7 +1466,7 @@ def unflatten_params(flat: torch.Tensor, num_classes: int) -> List[torch.Tensor]
 
 
 class FlatChain:
-    """The flat-parameter chain of an MTT iteration on the ``vdt_`` kernels (include/vd_traj.h, csrc/traj.hip): owns the
+    """The flat-parameter chain of an MTT iteration on the ``vdt_`` kernels (include/vd_hip.h, csrc/traj.hip): owns the
     reduction scratch, the 4-double loss record, the fp64 d/d syn_lr accumulator and the two vectors that live through the
     reverse sweep (thetabar, v), all sized on first use.  Vectors are contiguous fp32 tensors of one length on ``device``,
     16-byte aligned (fresh torch allocations and ``ExpertStore`` rows are)."""
@@ -1669,7 +1669,7 @@ class MTTTrainer:
             tape.append((ctx, share, handle, g))
             theta = flat.step(theta, g, self.syn_lr) if flat is not None else theta - self.syn_lr * g
         if flat is not None:
-            # ---- loss and reverse sweep on the vdt_ kernels (include/vd_traj.h) -----------------------
+            # ---- loss and reverse sweep on the vdt_ kernels (include/vd_hip.h) ------------------------
             record, _ = flat.loss(theta, theta0, target)
             grand = record[2].to(torch.float32)
             hv = None

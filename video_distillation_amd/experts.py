@@ -6,7 +6,7 @@ copies and two ``torch.cat`` (distill_baseline.py:213-221).
 
 Layout.  A file becomes one fp32 tensor (experts, epochs, Ppad); P = the 8 tensors' element count for ``num_classes``, Ppad = P
 rounded up to a multiple of 4 floats (padding zero), so every row starts on a 16-byte boundary -- what the ``vdt_`` kernels of
-include/vd_traj.h ask for (P is odd at 3 classes).
+include/vd_hip.h ask for (P is odd at 3 classes).
 
 Modes.  ``resident``: every file the walk will use lives on the device from construction on; refused, before anything is
 allocated there, when that is more than the device reports free.  ``host``: one file at a time in pinned host memory (a file is read, and its

@@ -24,9 +24,6 @@ SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernel
 CSRC_HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("frame_norm.h", "split16.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
 HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
-HEADER_TRAJ = os.path.join(_HERE, "..", "include", "vd_traj.h")      # the second public header: the vdt_ entry points (csrc/traj.hip)
-HEADER_STILL = os.path.join(_HERE, "..", "include", "vd_still.h")      # the third: the vds_ entry points (csrc/still.hip)
-HEADER_STILLROWS = os.path.join(_HERE, "..", "include", "vd_stillrows.h")      # the fourth: the vdsr_ entry points (csrc/still_rows.hip)
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
@@ -124,7 +121,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER, HEADER_TRAJ, HEADER_STILL, HEADER_STILLROWS, *CSRC_HEADERS)
+        key = _file_hash(src, HEADER, *CSRC_HEADERS)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -169,12 +166,12 @@ def library_stamp(path: str = None) -> Optional[str]:
 
 
 def sources_hash() -> str:
-    """sha256 (first 16 hex digits) over the kernel sources and the four ABI headers: what measurement files that are carried from one
-    run to the next (profiles/rNN_pmc_traffic.json -> bench.py's ``roofline.traffic``) are stamped with, so that a figure
-    measured on other kernels is refused instead of quoted."""
+    """sha256 (first 16 hex digits) over the kernel sources, the ABI header and the shared csrc headers: what measurement files
+    that are carried from one run to the next (profiles/rNN_pmc_traffic.json -> bench.py's ``roofline.traffic``) are stamped
+    with, so that a figure measured on other kernels is refused instead of quoted."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER, HEADER_TRAJ, HEADER_STILL, HEADER_STILLROWS] + CSRC_HEADERS:
+    for path in sorted(SOURCES) + [HEADER] + CSRC_HEADERS:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -187,9 +184,9 @@ _PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+"
 
 
 def parse_header(text: str, where: str = "include/vd_hip.h") -> dict:
-    """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses (names ``vd_*``, ``vdt_*`` for
-    include/vd_traj.h, ``vds_*`` for include/vd_still.h, ``vdsr_*`` for include/vd_stillrows.h) -> {name: (restype, [argtypes])}.  Anything else -- a type outside the set, a statement that is not wholly
-    a prototype -- is a ``ValueError`` that quotes it; no guesses."""
+    """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses (names ``vd_*`` and the three historical
+    prefixes ``vdt_*``, ``vds_*``, ``vdsr_*``) -> {name: (restype, [argtypes])}.  Anything else -- a type outside the set, a
+    statement that is not wholly a prototype -- is a ``ValueError`` that names ``where`` and quotes it; no guesses."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"typedef\s+struct\s*\w*\s*(\{[^{}]*\}\s*)?\w+\s*;", " ", text)
     text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|^[ \t]*\}[ \t]*$', " ", text, flags=re.M)      # (no directive is continued)
@@ -216,40 +213,6 @@ def signatures() -> dict:
         return parse_header(f.read())
 
 
-@functools.lru_cache(maxsize=None)
-def signatures_ext() -> dict:
-    """{name: (restype, [argtypes])} of include/vd_traj.h, the ``vdt_`` entry points of the same library (``signatures()`` and
-    ``EXPORTS`` are include/vd_hip.h alone)."""
-    with open(HEADER_TRAJ) as f:
-        sigs = parse_header(f.read(), "include/vd_traj.h")
-    other = [name for name in sigs if not name.startswith("vdt_")]
-    if other:
-        raise ValueError("include/vd_traj.h declares %s: its entry points carry the prefix vdt_" % ", ".join(other))
-    return sigs
-
-
-@functools.lru_cache(maxsize=None)
-def signatures_still() -> dict:
-    """{name: (restype, [argtypes])} of include/vd_still.h, the ``vds_`` entry points of the same library."""
-    with open(HEADER_STILL) as f:
-        sigs = parse_header(f.read(), "include/vd_still.h")
-    other = [name for name in sigs if not name.startswith("vds_")]
-    if other:
-        raise ValueError("include/vd_still.h declares %s: its entry points carry the prefix vds_" % ", ".join(other))
-    return sigs
-
-
-@functools.lru_cache(maxsize=None)
-def signatures_stillrows() -> dict:
-    """{name: (restype, [argtypes])} of include/vd_stillrows.h, the ``vdsr_`` entry points of the same library."""
-    with open(HEADER_STILLROWS) as f:
-        sigs = parse_header(f.read(), "include/vd_stillrows.h")
-    other = [name for name in sigs if not name.startswith("vdsr_")]
-    if other:
-        raise ValueError("include/vd_stillrows.h declares %s: its entry points carry the prefix vdsr_" % ", ".join(other))
-    return sigs
-
-
 def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
     if name == "EXPORTS":
         return tuple(signatures())
@@ -264,11 +227,9 @@ class _Library(ctypes.CDLL):
 
 
 def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
-    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h,
-    include/vd_traj.h, include/vd_still.h and include/vd_stillrows.h."""
+    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h."""
     L = _Library(path)
-    for name, (restype, argtypes) in list(signatures().items()) + list(signatures_ext().items()) + list(signatures_still().items()) \
-            + list(signatures_stillrows().items()):
+    for name, (restype, argtypes) in signatures().items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -469,31 +430,36 @@ def _still_tensor(t: torch.Tensor, dims: int, what: str) -> None:
         raise RuntimeError("%s has no CPU path: a contiguous fp32 tensor on a HIP device" % what)
 
 
+def _still_index(index, N: int, dev, what: str, checked: bool = False):
+    """``index`` of a still wrapper -> (n, its int64 table of n rows on ``dev``), (N, None) for None.  A HOST table (array, list,
+    CPU tensor) is checked here and uploaded with one copy, a device tensor is checked with one device reduction (a host read)
+    unless the caller says it has ``checked`` it.  ``ValueError`` for a row outside [0, N)."""
+    import numpy as np
+    if index is None:
+        return N, None
+    if isinstance(index, torch.Tensor) and index.is_cuda:
+        idx = index.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        bad = bool(((idx < 0) | (idx >= N)).any()) if idx.numel() and not checked else False
+    else:
+        host = np.ascontiguousarray(np.asarray(index, dtype=np.int64).reshape(-1))
+        bad = bool(host.size) and (int(host.min()) < 0 or int(host.max()) >= N)
+        idx = None if bad else torch.as_tensor(host).to(dev)
+    if bad:
+        raise ValueError("%s: an index outside [0, %d)" % (what, N))
+    return int(idx.numel()), idx
+
+
 def still_expand(images: torch.Tensor, index, T: int, checked: bool = False) -> torch.Tensor:
     """``vds_still_expand`` on the current stream: -> a fresh (n, T, 3, H, W) tensor, out[i, t] = images[index[i]] (``index``
-    None: out[i, t] = images[i]).  ``images`` (N, 3, H, W) contiguous fp32 on a HIP device.  ``index`` may repeat rows; a HOST
-    table (array, list, CPU tensor) is checked here and uploaded with one copy, a device tensor is checked with one device
-    reduction (a host read) unless the caller says it has ``checked`` it.  ``ValueError`` for a row outside [0, N): it never
-    reaches the kernel, which does not check."""
-    import numpy as np
+    None: out[i, t] = images[i]).  ``images`` (N, 3, H, W) contiguous fp32 on a HIP device.  ``index`` may repeat rows; a host
+    table or a device tensor, checked as ``_still_index`` says (``checked``: a device tensor the caller has checked).
+    ``ValueError`` for a row outside [0, N): it never reaches the kernel, which does not check."""
     _still_tensor(images, 4, "still_expand: images")
     N, H, W, T = int(images.shape[0]), int(images.shape[2]), int(images.shape[3]), int(T)
     if T < 1 or H < 1 or W < 1:
         raise ValueError("still_expand: T %d, H %d, W %d" % (T, H, W))
     dev = images.device
-    if index is None:
-        n, idx = N, None
-    else:
-        if isinstance(index, torch.Tensor) and index.is_cuda:
-            idx = index.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-            bad = bool(((idx < 0) | (idx >= N)).any()) if idx.numel() and not checked else False
-        else:
-            host = np.ascontiguousarray(np.asarray(index, dtype=np.int64).reshape(-1))
-            bad = bool(host.size) and (int(host.min()) < 0 or int(host.max()) >= N)
-            idx = None if bad else torch.as_tensor(host).to(dev)
-        if bad:
-            raise ValueError("still_expand: an index outside [0, %d)" % N)
-        n = int(idx.numel())
+    n, idx = _still_index(index, N, dev, "still_expand", checked)
     out = torch.empty((n, T, 3, H, W), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         run("vds_still_expand", ptr(images), ptr(idx), n, T, H, W, ptr(out), stream_ptr(dev))
@@ -506,29 +472,14 @@ def still_rows(images: torch.Tensor, index, T: int, prec: int, planes: int, out:
     planes whose leading part is written), byte for byte ``vd_pix2rows`` of ``still_expand(images, index, T)``.  ``prec`` one of
     the four codes ``PREC['bf16'] .. PREC['f16x3']`` (0..3); ``planes`` 2 also writes the low plane.  ``index`` is
     validated as ``still_expand`` validates it: ``ValueError`` for a row outside [0, N) before anything reaches the kernel."""
-    import numpy as np
     if images.dim() != 4 or int(images.shape[1]) != 3:
         raise ValueError("still_rows: images: a (n, 3, H, W) tensor, not %s" % (tuple(images.shape),))
     N, H, W, T = int(images.shape[0]), int(images.shape[2]), int(images.shape[3]), int(T)
     if T < 1 or H < 1 or W < 1 or prec not in (0, 1, 2, 3) or planes not in (1, 2):
         raise ValueError("still_rows: T %d, H %d, W %d, prec %r, planes %r" % (T, H, W, prec, planes))
-    host = None
-    if index is not None and not (isinstance(index, torch.Tensor) and index.is_cuda):      # a host table: checked before anything else
-        host = np.ascontiguousarray(np.asarray(index, dtype=np.int64).reshape(-1))
-        if host.size and (int(host.min()) < 0 or int(host.max()) >= N):
-            raise ValueError("still_rows: an index outside [0, %d)" % N)
-    _still_tensor(images, 4, "still_rows: images")
     dev = images.device
-    if index is None:
-        n, idx = N, None
-    else:
-        if host is None:
-            idx = index.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-            if idx.numel() and bool(((idx < 0) | (idx >= N)).any()):
-                raise ValueError("still_rows: an index outside [0, %d)" % N)
-        else:
-            idx = torch.as_tensor(host).to(dev)
-        n = int(idx.numel())
+    n, idx = _still_index(index, N, dev, "still_rows")      # (a bad table is refused before the device of ``images`` is looked at)
+    _still_tensor(images, 4, "still_rows: images")
     slots = n * T * 3 * H * ((W + 8 + 7) // 8)
     if out is None:
         out = torch.empty((planes, slots, 8), dtype=torch.int16, device=dev)

@@ -18,7 +18,7 @@ The expert trajectories of ``--buffer_path`` (``replay_buffer_N.pt`` of buffer.p
 ``--expert_store host`` keeps one file at a time in pinned host memory, ``resident`` all of them in HBM; ``--buffer_walk all``
 visits every file, ``reference`` only the first of the shuffle, as the reference's loops do (they never load a second file);
 ``--max_files`` bounds the files looked at.  ``--fused_flat on`` runs the flat-parameter arithmetic of an iteration on the
-``vdt_`` kernels (include/vd_traj.h), ``off`` on torch expressions.  The walk is seeded (``--seed``) and the same on every rank;
+``vdt_`` kernels (include/vd_hip.h), ``off`` on torch expressions.  The walk is seeded (``--seed``) and the same on every rank;
 every rank holds all memories and takes its share of each student batch (distill.MTTTrainer).
 
 Data as ``run_dm`` (``--dataset synthetic``, the reference's frame folders, or ``--data_file f.pt``; the test loaders, like the
