@@ -63,6 +63,39 @@ def load_static(path: str) -> torch.Tensor:
     return obj["image"].float()
 
 
+def save_keyframes(save_dir: str, it: int, frames: torch.Tensor, interp: str, T: int, best: bool = False) -> str:
+    """``keyframes_{it}.pt`` / ``keyframes_best.pt``: ``{"frames": (C*ipc,K,3,H,W) float32, "interp": str, "T": int}``, row
+    ``c*ipc + j`` (``run_dm --memories keyframes`` writes it; this project's own format: the reference stores whole clips)."""
+    from . import keyframes
+    if frames.dim() != 5 or frames.shape[2] != 3:
+        raise ValueError("save_keyframes: a (C*ipc, K, 3, H, W) tensor, not %s" % (tuple(frames.shape),))
+    keyframes.table(int(T), int(frames.shape[1]), interp)          # (refuses a K / T / interp no table exists for)
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, "keyframes_%d.pt" % it)
+    blob = {"frames": frames.detach().cpu().float().clone(), "interp": str(interp), "T": int(T)}
+    torch.save(blob, path)
+    if best:
+        torch.save(blob, os.path.join(save_dir, "keyframes_best.pt"))
+    return path
+
+
+def load_keyframes(path: str):
+    """-> (frames (C*ipc,K,3,H,W) float32, interp, T) of a ``keyframes_*.pt``."""
+    obj = torch.load(path, map_location="cpu")
+    if not isinstance(obj, dict) or not all(k in obj for k in ("frames", "interp", "T")):
+        raise KeyError('a key-frame file is a dict with the keys "frames", "interp" and "T"')
+    return obj["frames"].float(), str(obj["interp"]), int(obj["T"])
+
+
+def keyframes_to_images(path: str) -> torch.Tensor:
+    """The clips a ``keyframes_*.pt`` stands for, (C*ipc,T,3,H,W) float32 on the host -- what ``images_*.pt`` holds, so the
+    result can be evaluated by the reference or be the init of ``run_mtt --memories images``.  The same products and adds, in
+    the same order, as the device expansion."""
+    from . import keyframes
+    frames, interp, T = load_keyframes(path)
+    return keyframes.expand_torch(frames, keyframes.table(T, int(frames.shape[1]), interp))
+
+
 def load_hallucinators(path: str):
     """-> list of (weight, bias) from a ``hal_{it}.pt`` / ``weights_best.pt`` state dict."""
     state = torch.load(path, map_location="cpu")

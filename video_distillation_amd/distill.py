@@ -445,6 +445,13 @@ class HipBackend:
     def still_reduce(self, g_clips):
         return self.hip.still_reduce(g_clips.contiguous())
 
+    def keyframe_expand(self, keys, table):
+        """(n,K,3,H,W) key frames -> (n,T,3,H,W) clips by ``table`` (keyframes.Table) on the current stream."""
+        return self.hip.keyframe_expand(keys, table)
+
+    def keyframe_reduce(self, g_clips, table):
+        return self.hip.keyframe_reduce(g_clips.contiguous(), table)
+
     def embed_keep(self, x: torch.Tensor):
         return self.eng_syn.forward(x, keep=True)
 
@@ -1443,6 +1450,89 @@ class StillDMTrainer(DMTrainer):
         import types
         return DMTrainer.gather_syn(types.SimpleNamespace(world=self.world, num_classes=self.num_classes, ipc=self.spc,
                                                           image_syn=self.static, owned_classes=self.owned_classes))
+
+
+def keyframe_expand(be, keys: torch.Tensor, table) -> torch.Tensor:
+    """(n,K,3,H,W) -> (n,T,3,H,W): ``be.keyframe_expand`` where the backend has one (HipBackend: ``vdk_keyframe_expand``), the
+    torch expression with the same operation order otherwise (the CPU oracle backend)."""
+    if hasattr(be, "keyframe_expand"):
+        return be.keyframe_expand(keys, table)
+    from . import keyframes
+    return keyframes.expand_torch(keys, table)
+
+
+def keyframe_reduce(be, g: torch.Tensor, table) -> torch.Tensor:
+    """(n,T,3,H,W) -> (n,K,3,H,W), the adjoint of ``keyframe_expand``: ``be.keyframe_reduce`` / ``vdk_keyframe_reduce``, or the
+    same products and adds in torch."""
+    if hasattr(be, "keyframe_reduce"):
+        return be.keyframe_reduce(g, table)
+    from . import keyframes
+    return keyframes.reduce_torch(g, table)
+
+
+class KeyframeDMTrainer(DMTrainer):
+    """Distribution matching on KEY-FRAME memories: each memory is ``K`` learned frames, ``keys`` (n_owned*ipc, K, 3, H, W) with a
+    momentum buffer of that shape, brought to the network's T frames by a fixed two-tap table (``keyframes.table(T, K, interp)``:
+    the paper's segments for ``'nearest'``, linear interpolation with aligned end points for ``'linear'``).  K = 1 is the still
+    clip of ``StillDMTrainer``'s synthetic side, K = T is ``DMTrainer`` itself, bit for bit.
+
+    Real side: ``DMTrainer``'s, untouched -- real clips stay clips.  Synthetic side, all on the synthetic-clip stream:
+    ``image_syn = keyframe_expand(keys)`` goes through ``embed_syn``; the clip gradient is folded onto the keys
+    (``keyframe_reduce``, the adjoint, in a fixed order), SGD with momentum steps ``keys``, and ``image_syn`` is expanded again
+    for the next step -- inside ``_apply_pixel_grad``, so ``step(it, overlap=True)`` and the deferred backward keep their order.
+
+    Pooling ties: under ``'nearest'`` the frames of one segment are equal, so the temporal max-pool meets exact ties between
+    them; ``StillGMTrainer``'s argument applies per key (a tie moves gradient between equal frames of one key, and those are
+    summed with equal weights)."""
+
+    def __init__(self, backend, pool: RealPool, geo: P.NetGeometry, num_classes: int, ipc: int, batch_real: int, lr_img: float,
+                 key_frames: int = 4, interp: str = "linear", momentum: float = 0.5, rank: int = 0, world: int = 1,
+                 keys: Optional[torch.Tensor] = None, shard: str = "class", exchange: str = "owner"):
+        from . import keyframes
+        if exchange != "owner":
+            raise ValueError("KeyframeDMTrainer: exchange=%r is a benchmark leg of the clip trainer; the key-frame trainer is owner-computes" % (exchange,))
+        clips = pool.clips
+        if clips.dim() != 5 or tuple(clips.shape[1:]) != (geo.frames, 3, geo.height, geo.width):
+            raise ValueError("KeyframeDMTrainer: a pool of clips (N, %d, 3, %d, %d), not %s" % (geo.frames, geo.height, geo.width, tuple(clips.shape)))
+        self.geo, self.table = geo, keyframes.table(geo.frames, key_frames, interp)
+        self.key_frames, self.interp = int(key_frames), interp
+        # the base class decides the sharding on an empty memory; the keys, their momentum and the clips follow once the classes
+        # this rank owns are known
+        super().__init__(backend, pool, num_classes, ipc, batch_real, lr_img, momentum=momentum, rank=rank, world=world,
+                         image_syn=clips[:0], shard=shard, exchange=exchange)
+        owned = self.classes
+        if keys is None:          # --init real: the first ipc clips of each owned class, key k from frame init_frames[k]
+            idx = np.concatenate([pool.offsets[c] + np.arange(ipc) % pool.counts[c] for c in owned]) if owned \
+                else np.zeros(0, dtype=np.int64)
+            frames = torch.as_tensor(keyframes.init_frames(geo.frames, self.key_frames, interp), device=clips.device, dtype=torch.int64)
+            keys = clips[torch.as_tensor(idx, device=clips.device, dtype=torch.int64)].index_select(1, frames).clone()
+        if tuple(keys.shape) != (len(owned) * ipc, self.key_frames, 3, geo.height, geo.width):
+            raise ValueError("KeyframeDMTrainer: keys %s for %d owned classes x ipc %d x %d key frames"
+                             % (tuple(keys.shape), len(owned), ipc, self.key_frames))
+        self.keys = keys.contiguous()
+        self.buf = torch.zeros_like(self.keys)          # momentum of the KEYS
+        self.image_syn = self._expand_keys()
+
+    def _expand_keys(self) -> torch.Tensor:
+        """``keyframe_expand(keys)`` as a fresh tensor that the synthetic-clip stream may read."""
+        x = keyframe_expand(self.be, self.keys, self.table)
+        if getattr(self.be, "two_streams", False):
+            x.record_stream(self.be.s_syn)
+        return x
+
+    def _apply_pixel_grad(self, grad: torch.Tensor, first: bool) -> None:
+        be = self.be
+        be.sgd(self.keys, self.buf, keyframe_reduce(be, grad, self.table), self.lr_img, self.momentum, first=first)
+        self.image_syn = self._expand_keys()          # the clips of the next step
+
+    def gather_keys(self) -> torch.Tensor:
+        """All ranks' keys in class order on every rank: row ``c*ipc + j`` (``keyframes_*.pt``), after the steps in flight."""
+        self.sync()
+        if not collectives_on(self.world):
+            return self.keys
+        import types
+        return DMTrainer.gather_syn(types.SimpleNamespace(world=self.world, num_classes=self.num_classes, ipc=self.ipc,
+                                                          image_syn=self.keys, owned_classes=self.owned_classes))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -20,10 +20,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvd_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernels.hip", "program.hip", "planner.cpp", "comm.cpp",
                                                          "coreset.hip", "clips_sample.hip", "eval_stats.hip", "still.hip", "still_rows.hip",
-                                                         "traj.hip")]
+                                                         "keyframes.hip", "traj.hip")]
 CSRC_HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("frame_norm.h", "split16.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
 HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
+KEYFRAME_HEADER = os.path.join(_HERE, "..", "include", "vd_keyframes.h")      # the vdk_* entry points (csrc/keyframes.hip): under both hashes too
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
@@ -121,7 +122,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER, *CSRC_HEADERS)
+        key = _file_hash(src, HEADER, KEYFRAME_HEADER, *CSRC_HEADERS)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -171,7 +172,7 @@ def sources_hash() -> str:
     with, so that a figure measured on other kernels is refused instead of quoted."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER] + CSRC_HEADERS:
+    for path in sorted(SOURCES) + [HEADER, KEYFRAME_HEADER] + CSRC_HEADERS:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -179,20 +180,24 @@ def sources_hash() -> str:
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
 _RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None, "const char*": ctypes.c_char_p}
-_PROTOTYPE = re.compile(r"(int64_t|int|void|const char\s*\*)\s*(vd(?:t|s|sr)?_[a-z0-9_]+)\s*\(([^()]*)\)")
+NAME_PATTERN = r"vd(?:t|s|sr)?_[a-z0-9_]+"          # include/vd_hip.h: vd_* and its three historical prefixes
+KEYFRAME_NAME_PATTERN = r"vdk_[a-z0-9_]+"          # include/vd_keyframes.h
+_PROTOTYPE = r"(int64_t|int|void|const char\s*\*)\s*(%s)\s*\(([^()]*)\)"
 _PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+")
 
 
-def parse_header(text: str, where: str = "include/vd_hip.h") -> dict:
-    """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses (names ``vd_*`` and the three historical
-    prefixes ``vdt_*``, ``vds_*``, ``vdsr_*``) -> {name: (restype, [argtypes])}.  Anything else -- a type outside the set, a
-    statement that is not wholly a prototype -- is a ``ValueError`` that names ``where`` and quotes it; no guesses."""
+def parse_header(text: str, where: str = "include/vd_hip.h", names: str = NAME_PATTERN) -> dict:
+    """The prototypes of a C header in the closed set of spellings include/vd_hip.h uses -> {name: (restype, [argtypes])}.
+    ``names``: the regular expression a function name has to match in full (default: ``vd_*`` and the three historical prefixes
+    ``vdt_*``, ``vds_*``, ``vdsr_*``).  Anything else -- another name, a type outside the set, a statement that is not wholly a
+    prototype -- is a ``ValueError`` that names ``where`` and quotes it; no guesses."""
+    prototype = re.compile(_PROTOTYPE % names)
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"typedef\s+struct\s*\w*\s*(\{[^{}]*\}\s*)?\w+\s*;", " ", text)
     text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|^[ \t]*\}[ \t]*$', " ", text, flags=re.M)      # (no directive is continued)
     sigs = {}
     for stmt in filter(None, (" ".join(part.split()) for part in text.split(";"))):
-        m = _PROTOTYPE.fullmatch(stmt)
+        m = prototype.fullmatch(stmt)
         if m is None or m.group(2) in sigs:
             raise ValueError("%s: not a prototype the binding understands, or a second one of its name: %r" % (where, stmt))
         ret, name, params = m.group(1).replace(" *", "*"), m.group(2), m.group(3).strip()
@@ -213,6 +218,13 @@ def signatures() -> dict:
         return parse_header(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def keyframe_signatures() -> dict:
+    """{name: (restype, [argtypes])} of include/vd_keyframes.h (the ``vdk_*`` entry points), read and parsed once."""
+    with open(KEYFRAME_HEADER) as f:
+        return parse_header(f.read(), "include/vd_keyframes.h", KEYFRAME_NAME_PATTERN)
+
+
 def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
     if name == "EXPORTS":
         return tuple(signatures())
@@ -227,9 +239,10 @@ class _Library(ctypes.CDLL):
 
 
 def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
-    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h."""
+    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h and
+    include/vd_keyframes.h."""
     L = _Library(path)
-    for name, (restype, argtypes) in signatures().items():
+    for name, (restype, argtypes) in list(signatures().items()) + list(keyframe_signatures().items()):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -502,6 +515,67 @@ def still_reduce(g_clips: torch.Tensor) -> torch.Tensor:
     out = torch.empty((n, 3, H, W), dtype=torch.float32, device=g_clips.device)
     with torch.cuda.device(g_clips.device):
         run("vds_still_reduce", ptr(g_clips), n, T, H, W, ptr(out), stream_ptr(g_clips.device))
+    return out
+
+
+VDK_MAX_FRAMES = 64          # include/vd_keyframes.h
+
+
+class VdkTable(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_int32), ("K", ctypes.c_int32), ("i0", ctypes.c_int32 * VDK_MAX_FRAMES), ("i1", ctypes.c_int32 * VDK_MAX_FRAMES),
+                ("w0", ctypes.c_float * VDK_MAX_FRAMES), ("w1", ctypes.c_float * VDK_MAX_FRAMES)]
+
+
+def vdk_table(table) -> VdkTable:
+    """The ctypes mirror of a ``keyframes.Table`` (anything with ``T``, ``K`` and the four length-T arrays): host memory, passed
+    by address; the library copies it into the kernel arguments.  ``ValueError`` for what ``vdk_table_check`` would refuse."""
+    if isinstance(table, VdkTable):
+        return table
+    if getattr(table, "_vdk", None) is not None:          # (a keyframes.Table keeps its mirror: built and checked once, not per step)
+        return table._vdk
+    T, K = int(table.T), int(table.K)
+    if not (1 <= K <= T <= VDK_MAX_FRAMES) or any(len(a) != T for a in (table.i0, table.i1, table.w0, table.w1)):
+        raise ValueError("key-frame table: T %d, K %d, arrays of %s entries" % (T, K, [len(a) for a in (table.i0, table.i1, table.w0, table.w1)]))
+    c = VdkTable()
+    c.T, c.K = T, K
+    for t in range(T):
+        c.i0[t], c.i1[t], c.w0[t], c.w1[t] = int(table.i0[t]), int(table.i1[t]), float(table.w0[t]), float(table.w1[t])
+    if lib().vdk_table_check(ctypes.addressof(c)) != 0:
+        raise ValueError("key-frame table: an index outside [0, %d) or a weight that is not finite" % K)
+    if hasattr(table, "_vdk"):
+        table._vdk = c
+    return c
+
+
+def _keyframe_tensor(t: torch.Tensor, frames: int, what: str) -> None:
+    if t.dim() != 5 or int(t.shape[1]) != frames or int(t.shape[2]) != 3 or int(t.shape[3]) < 1 or int(t.shape[4]) < 1:
+        raise ValueError("%s: a (n, %d, 3, H, W) tensor, not %s" % (what, frames, tuple(t.shape)))
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise RuntimeError("%s has no CPU path: a contiguous fp32 tensor on a HIP device" % what)
+
+
+def keyframe_expand(keys: torch.Tensor, table) -> torch.Tensor:
+    """``vdk_keyframe_expand`` on the current stream: (n, K, 3, H, W) -> a fresh (n, T, 3, H, W) tensor, frame t =
+    w0[t] * key i0[t] + w1[t] * key i1[t] (``table``: a ``keyframes.Table`` or a ``VdkTable``).  ``keys`` contiguous fp32 on a
+    HIP device; shapes and the table are checked here, on the host."""
+    tab = vdk_table(table)
+    _keyframe_tensor(keys, tab.K, "keyframe_expand: keys")
+    n, _, _, H, W = (int(v) for v in keys.shape)
+    out = torch.empty((n, tab.T, 3, H, W), dtype=torch.float32, device=keys.device)
+    with torch.cuda.device(keys.device):
+        run("vdk_keyframe_expand", ptr(keys), n, ctypes.addressof(tab), H, W, ptr(out), stream_ptr(keys.device))
+    return out
+
+
+def keyframe_reduce(g_clips: torch.Tensor, table) -> torch.Tensor:
+    """``vdk_keyframe_reduce`` on the current stream: (n, T, 3, H, W) -> a fresh (n, K, 3, H, W) tensor, the adjoint of
+    ``keyframe_expand``: per key the products w * g[t] of its terms, added in ascending t (bitwise repeatable)."""
+    tab = vdk_table(table)
+    _keyframe_tensor(g_clips, tab.T, "keyframe_reduce: g_clips")
+    n, _, _, H, W = (int(v) for v in g_clips.shape)
+    out = torch.empty((n, tab.K, 3, H, W), dtype=torch.float32, device=g_clips.device)
+    with torch.cuda.device(g_clips.device):
+        run("vdk_keyframe_reduce", ptr(g_clips), n, ctypes.addressof(tab), H, W, ptr(out), stream_ptr(g_clips.device))
     return out
 
 

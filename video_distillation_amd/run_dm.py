@@ -26,6 +26,16 @@ They are written at ``--memories images``' cadence (a new best, or an evaluation
 deviation, which is ``run_dc --memories static``'s: with ``--no_eval``, or data without test images, the evaluation iterations
 that are multiples of 1000 still write their file (``--memories images`` writes nothing then) -- the file is this stage's
 product, and a run that cannot evaluate would otherwise leave none.
+
+``--memories keyframes`` learns KEY-FRAME memories (``distill.KeyframeDMTrainer``): ``--key_frames K`` frames per synthetic clip,
+brought to ``--frames`` frames on the device by repeating them over segments (``--interp nearest``) or by linear interpolation
+along T (``--interp linear``); K = 1 is a still, K = ``--frames`` the clip.  Real clips, data, sharding and evaluation are those of
+``--memories images`` (evaluation trains on the expanded clips); ``--init noise`` is drawn in full on the host from ``--seed`` and
+sliced per rank.  Files: ``keyframes_{it}.pt`` / ``keyframes_best.pt`` = ``{"frames": (C*ipc,K,3,H,W), "interp", "T"}`` under
+``save_path/Keyframes_DM/{dataset}_ipc{ipc}_k{K}_{interp}_{lr_img}``, at ``--memories images``' cadence;
+``checkpoint.keyframes_to_images(path)`` gives the ``images_*.pt`` tensor of such a file.
+
+    python -m video_distillation_amd.run_dm --memories keyframes --key_frames 4 --interp linear --dataset miniUCF101 --data_path D
 """
 from __future__ import annotations
 
@@ -62,11 +72,15 @@ def build_parser():
     p.add_argument('--pool_per_class', type=int, default=93, help='synthetic data only')
     p.add_argument('--prec_real', type=str, default='f16')
     p.add_argument('--prec_syn', type=str, default='f16x3')
-    p.add_argument('--memories', type=str, default='images', choices=['images', 'static'],
+    p.add_argument('--memories', type=str, default='images', choices=['images', 'static', 'keyframes'],
                    help="images: synthetic clips (images_{it}.pt); static: synthetic still images (static_{it}.pt; unlike images, "
-                        "also written at evaluation iterations that are multiples of 1000 when nothing is evaluated)")
+                        "also written at evaluation iterations that are multiples of 1000 when nothing is evaluated); keyframes: "
+                        "--key_frames learned frames per clip, expanded to --frames on the device (keyframes_{it}.pt)")
     p.add_argument('--spc', type=int, default=2, help='--memories static: images per class')
-    p.add_argument('--seed', type=int, default=0, help='--memories static: seed of --init noise')
+    p.add_argument('--seed', type=int, default=0, help='--memories static / keyframes: seed of --init noise')
+    p.add_argument('--key_frames', type=int, default=4, help='--memories keyframes: learned frames per synthetic clip (1 .. --frames)')
+    p.add_argument('--interp', type=str, default='linear', choices=['linear', 'nearest'],
+                   help='--memories keyframes: linear interpolation along T, or each key repeated over its segment')
     driver.add_data_flags(p)
     driver.add_eval_flags(p)
     return p
@@ -156,10 +170,70 @@ def run_static(args, backend=None, log=None, shard: str = "class", exchange: str
     return trainer
 
 
+def run_keyframes(args, backend=None, log=None, shard: str = "class", exchange: str = "owner"):
+    """``--memories keyframes``: the loop of ``run`` on ``distill.KeyframeDMTrainer``."""
+    from . import checkpoint, distill, keyframes, plan, utils
+    K, T = args.key_frames, args.frames
+    keyframes.table(T, K, args.interp)          # (the refusals, before any data is loaded)
+    rank, world, device = driver.start(use_cuda=backend is None)
+    geo = plan.NetGeometry(T, args.im_size, args.im_size)
+    pool, num_classes, (c_lo, c_hi), testloader = load_data(args, rank, world, geo, device)
+    if backend is None:
+        backend = distill.HipBackend(geo, device, prec_real=args.prec_real, prec_syn=args.prec_syn)
+    keys = None
+    if args.init == 'noise':
+        gen = torch.Generator().manual_seed(args.seed)          # drawn in full on the host: every sharding starts from the same state
+        keys = torch.randn((num_classes * args.ipc, K, 3, args.im_size, args.im_size), generator=gen)
+        owned = list(range(c_lo, c_hi))
+        if shard == "hybrid" and world > 1:          # (the rows of a rank's memories: DMTrainer.owned_classes)
+            block, _, split_owned = distill.hybrid_partition(num_classes, rank, world)
+            owned = block + split_owned
+        rows = [c * args.ipc + j for c in owned for j in range(args.ipc)]
+        keys = keys[rows].to(device)
+    trainer = distill.KeyframeDMTrainer(backend, pool, geo, num_classes, args.ipc, args.batch_real, args.lr_img, key_frames=K,
+                                        interp=args.interp, momentum=0.5, rank=rank, world=world, keys=keys, shard=shard, exchange=exchange)
+    eval_pool = utils.get_eval_pool(args.eval_mode, args.model, args.model)
+    best_acc = {m: 0.0 for m in eval_pool}; best_std = {m: 0.0 for m in eval_pool}
+    save_dir = os.path.join(args.save_path, "Keyframes_DM", "%s_ipc%d_k%d_%s_%s" % (args.dataset, args.ipc, K, args.interp, args.lr_img))
+    log = driver.JsonLog(args.log_file, rank, log)
+    eval_seed = None
+    if args.eval_ranks == 'all' and not args.no_eval:
+        eval_seed = driver.draw_eval_seed(args.eval_seed, rank, world)
+        log.emit({"eval_ranks": "all", "eval_seed": eval_seed, "world": world})
+    label_syn = torch.arange(num_classes).repeat_interleave(args.ipc)
+    eval_its = set(np.arange(0, args.Iteration + 1, args.eval_it).tolist())
+    t0 = time.time()
+    for it in range(args.Iteration + 1):
+        if it in eval_its and not args.no_eval:
+            syn_all = trainer.gather_syn()          # (collectives: every rank, whoever evaluates or saves)
+            keys_all = trainer.gather_keys()
+            trainer.sync()
+            save_best = False
+            if testloader is not None:
+                save_best, pooled = driver.evaluate_round(
+                    args, it, syn_all.detach().clone(), label_syn, 'none', args.lr_net, testloader, eval_pool, best_acc, best_std, log,
+                    rank=rank, world=world, device=device, num_classes=num_classes,
+                    pool_seed=None if eval_seed is None else eval_seed + it)
+                for got in pooled:
+                    log.emit({"step": it, "eval_pool": {"train_s": got["times"]["train_s"], "test_pass_s": got["times"]["test_pass_s"],
+                                                        "assignment": got["assignment"]}})
+            if rank == 0 and (save_best or it % 1000 == 0):
+                checkpoint.save_keyframes(save_dir, it, keys_all, args.interp, T, best=save_best)
+        loss = trainer.global_loss(trainer.step(it, overlap=True))
+        if it % 10 == 0 or it == args.Iteration:
+            trainer.sync()
+            log.emit({"step": it, "Loss": float(loss) / num_classes, "elapsed_s": round(time.time() - t0, 3)})
+    trainer.sync()
+    log.close()
+    return trainer
+
+
 def run(args, backend=None, log=None, shard: str = "class", exchange: str = "owner"):
     from . import checkpoint, distill, plan, utils
     if getattr(args, 'memories', 'images') == 'static':
         return run_static(args, backend, log, shard=shard, exchange=exchange)
+    if getattr(args, 'memories', 'images') == 'keyframes':
+        return run_keyframes(args, backend, log, shard=shard, exchange=exchange)
     rank, world, device = driver.start(use_cuda=backend is None)
     geo = plan.NetGeometry(args.frames, args.im_size, args.im_size)
     pool, num_classes, (c_lo, c_hi), testloader = load_data(args, rank, world, geo, device)
