@@ -123,6 +123,73 @@ def run_plan(plan, src, w_flat, bias, nclips, out):
     return arg
 
 
+def clip_minor(x, nclips):
+    """What vd_clip_minor_cl / _pix produce (before 16-bit rounding): [cin][clip/8][t*h*w][8 clips], absent clips zero."""
+    cin = x.shape[1]
+    ccb = -(-nclips // 8)
+    out = np.zeros((cin, ccb * 8, int(np.prod(x.shape[2:]))))
+    out[:, :nclips] = np.asarray(x, dtype=np.float64)[:nclips].reshape(nclips, cin, -1).transpose(1, 0, 2)
+    return out.reshape(cin, ccb, 8, -1).transpose(0, 1, 3, 2).copy()
+
+
+def run_wgrad_plan(plan, x, dy, nclips):
+    """The weight-gradient tile program (plan.plan_wgrad) in fp64, from the tables the device reads: flat_tables(), gather_table(),
+    ``boxes`` (word 5 = accumulation copy) and the packed-dy layout of plan.wgrad_pack_index.
+    x (nclips, cin, t, h, w), dy (nclips, cout, T, OH, OW) -> dW (cout, cin, 3, 7, 7).
+
+    A 'clip' of the program is an input channel, its channel chunks are the chunks of 8 clips of the clip-minor source; per box
+    the patch is gathered with zero fill, K step s / lane half hh multiplies A = patch[a_off + tap_off[2 s + hh]] (rows = taps, 8
+    clips) by the box's packed dy (32 output channels x 8 clips per N tile), and the live rows of the row table are added into
+    copy box[5] of the [cin][tap][cout] target; the copies are folded at the end."""
+    descs, tables = plan.flat_tables()
+    gather = plan.gather_table()
+    src = clip_minor(x, nclips)                             # [cin, CCb, npos, 8]
+    cin = src.shape[0]
+    src_flat = src.reshape(cin, plan.CC, -1)               # 16-bit ELEMENTS of one (channel, clip chunk)
+    assert src.shape[1] == plan.CC and plan.ncl == 1 and plan.epi == P.EPI_ROWS and plan.atomic and plan.n_stride == 1
+    dyf = np.asarray(dy, dtype=np.float64)[:nclips].transpose(0, 2, 3, 4, 1).reshape(-1)          # [clip][t][oh][ow][n]
+    idx = P.wgrad_pack_index(plan)                          # [nbox, CCb, S, NT, 64, 8]
+    assert idx.max() < dyf.size
+    assert plan.w_box_stride == plan.CC * plan.S * plan.NT * 64 * 8
+    replicas = int(plan.meta["replicas"])
+    ncol = plan.NT * 32
+    assert ncol == plan.n_out
+    rep = np.zeros((replicas, cin * plan.out_clip_stride))
+    k8 = np.arange(8)
+    for bi, box in enumerate(plan.boxes):
+        ty, out_rel, copy = int(box[0]), int(box[4]), int(box[5])
+        assert 0 <= copy < replicas, "box %d accumulates into copy %d of %d" % (bi, copy, replicas)
+        pitch_c, mt, a_ofs, o_ofs, t_ofs = [int(v) for v in descs[ty][5:10]]
+        a_off, rem_a = np.divmod(tables[a_ofs:a_ofs + mt * 32].astype(np.int64), 16)
+        tap_off, rem_t = np.divmod(tables[t_ofs:t_ofs + 2 * plan.S].astype(np.int64), 16)
+        assert not rem_a.any() and not rem_t.any(), "LDS offsets are whole 16-byte slots"
+        out_tab = tables[o_ofs:o_ofs + mt * 32].astype(np.int64)
+        live = np.where(out_tab >= 0)[0]
+        assert live.size == 147 and (out_tab[live] == np.arange(147) * plan.n_out).all(), "147 live rows at tap * cout"
+        gt = gather[bi][:pitch_c].astype(np.int64)
+        fill = np.where(gt >= 0)[0]
+        assert ((gt[fill] >> 24) == 0).all(), "one 'clip' (input channel) per box"
+        o2 = 2 * (gt[fill] & 0xFFFFFF)                      # dword offset -> element offset
+        assert fill.size == 0 or (o2.min() >= 0 and o2.max() + 8 <= src_flat.shape[2]), \
+            "%s box %d gathers elements up to %d of a %d-element chunk" % (plan.name, bi, o2.max() + 8, src_flat.shape[2])
+        sl = a_off[live][None, :] + tap_off[:, None]        # [2S, 147] patch slots of (step position, tap row)
+        assert sl.min() >= 0 and sl.max() < pitch_c, "%s box %d reads slot %d of a %d-slot patch" % (plan.name, bi, sl.max(), pitch_c)
+        for cb in range(plan.CC):
+            patch = np.zeros((cin, pitch_c, 8))
+            patch[:, fill] = src_flat[:, cb][:, o2[:, None] + k8[None, :]]
+            bsel = idx[bi, cb]                              # [S, NT, 64, 8]
+            bop = np.where(bsel >= 0, dyf[np.maximum(bsel, 0)], 0.0)
+            # K index = (step s, lane half hh, clip k); a lane's column is lane & 31
+            bmat = bop.reshape(plan.S, plan.NT, 2, 32, 8).transpose(0, 2, 4, 1, 3).reshape(plan.S * 16, ncol)
+            amat = patch[:, sl].transpose(0, 2, 1, 3).reshape(cin * 147, plan.S * 16)      # [(channel, tap row), K]
+            acc = (amat @ bmat).reshape(cin, 147, ncol)
+            for c in range(cin):
+                base = c * plan.out_clip_stride + out_rel
+                rep[copy, (base + out_tab[live])[:, None] + np.arange(ncol)[None, :]] += acc[c]
+    dw = rep.sum(axis=0).reshape(cin, 147, plan.n_out)
+    return dw.transpose(2, 0, 1).reshape(plan.n_out, cin, P.KT, P.KH, P.KW)
+
+
 def pix_to_rows(x_btchw):
     """What vd_pix2rows produces: [B, 1, T*3, H, pitch] with 3 leading zero pixels per row."""
     B, T, C, H, W = x_btchw.shape

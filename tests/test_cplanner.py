@@ -121,7 +121,8 @@ def test_both_planners_refuse_the_same_clips(dims):
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libvd_hip.so not built")
 @pytest.mark.parametrize("dims,nclips,planes", [((16, 112, 112), 64, 2), ((16, 112, 112), 64, 1), ((16, 112, 112), 5, 2), ((8, 64, 64), 256, 2),
-                                                ((8, 64, 64), 50, 1), ((8, 80, 96), 7, 2), ((4, 64, 64), 3, 1)])
+                                                ((8, 64, 64), 50, 1), ((8, 80, 96), 7, 2), ((4, 64, 64), 3, 1),
+                                                ((4, 64, 66), 9, 2), ((4, 65, 63), 1, 1), ((4, 70, 58), 9, 2), ((4, 70, 58), 33, 1)])
 def test_cpp_planner_emits_the_python_planner_s_weight_gradient_programs(dims, nclips, planes):
     """vd_program_build_wgrad == plan.plan_wgrad: the same block of positions, the same accumulation copies, byte-identical
     serialised programs, for every layer of the benchmark geometries and an odd one, both operand-plane counts, batch sizes

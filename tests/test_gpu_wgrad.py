@@ -50,7 +50,10 @@ def test_wgrad_matches_autograd(prec, tol, cfg):
 
 @pytest.mark.parametrize("prec", ["f16x3", "f16", "bf16x3"])
 @pytest.mark.parametrize("cfg", [(64, 8, 32, 32, 1, 11, 1, None), (128, 8, 16, 16, 2, 5, 0, None), (64, 4, 14, 14, 1, 9, 1, None),
-                                 (128, 8, 14, 14, 2, 9, 1, "4,7,7"), (64, 6, 14, 14, 1, 3, 0, "4,4,14"), (128, 8, 8, 8, 2, 16, 1, "1,2,2")])
+                                 (128, 8, 14, 14, 2, 9, 1, "4,7,7"), (64, 6, 14, 14, 1, 3, 0, "4,4,14"), (128, 8, 8, 8, 2, 16, 1, "1,2,2"),
+                                 # grids with odd OH or OW: a last conv row / column that no pool window covers
+                                 (64, 4, 33, 32, 1, 3, 1, None), (64, 4, 35, 29, 1, 3, 0, None), (128, 4, 9, 7, 2, 9, 1, None),
+                                 (128, 4, 9, 7, 2, 9, 1, "1,3,3")])
 def test_fused_unpool_pack_is_bitwise_the_two_kernel_path(prec, cfg, monkeypatch):
     """vd_unpool_relu_bwd_packed == vd_unpool_relu_bwd followed by vd_pack_dy, bit for bit, for both gradient layouts,
     both pool depths, ragged clip counts (not a multiple of 8) and grids the block does not divide."""

@@ -141,7 +141,6 @@ class TrainEngine:
         main = torch.cuda.current_stream(self.device)
         side = self._side_stream() if (self.side_wgrad and g is not None) else None
         for li in (2, 1, 0):
-            cout, To, Ho, Wo, pt = eng.dims[li][1], *eng.dims[li][8:12]
             dense = li > 0 or dx is not None or keep_dense   # the first layer's dense dy: pixel-gradient and second-order passes only
             if not dense and g is None:
                 break
@@ -150,28 +149,38 @@ class TrainEngine:
                 if side is not None:
                     side.wait_stream(main)          # the level's gradient and its scale are queued on the main stream
                 with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                    # bias gradient from the pooled gradient (the dense dy has one non-zero per live pool window)
-                    if hip.deterministic():
-                        nsc = int(hip.lib().vd_bias_grad_pooled_scratch_floats(nb, cout, To * Ho * Wo))
-                        bsc = eng._buf("bias_part%d" % li, (nsc,), torch.float32)
-                        hip.run("vd_bias_grad_pooled_ordered", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To * Ho * Wo, layout,
-                                hip.ptr(bsc), hip.ptr(g[2 * li + 1]), hip.stream_ptr(self.device))
-                    else:
-                        hip.run("vd_bias_grad_pooled", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To * Ho * Wo, layout,
-                                hip.ptr(g[2 * li + 1]), hip.stream_ptr(self.device))
-                    op = self._wgrad(li, nb)
-                    # pooled gradient -> packed B operand of the weight-gradient program in one pass (4-8x fewer bytes than
-                    # re-reading the dense slots, which for the first layer are not even written when nobody else needs them)
                     if li == 0:
-                        op.run_pooled(x, True, 0, grad, am[0], layout, (To, Ho, Wo, pt), sc, g[0], out_scale=inv)
+                        self.level_param_grads(0, nb, grad, layout, am[0], x, True, 0, sc, inv, g[0], g[1])
                     else:
-                        op.run_pooled(acts[li], False, act_plane[li], grad, am[li], layout, (To, Ho, Wo, pt), sc, g[2 * li], out_scale=inv)
+                        self.level_param_grads(li, nb, grad, layout, am[li], acts[li], False, act_plane[li], sc, inv, g[2 * li], g[2 * li + 1])
             if li > 0 or dx is not None:
                 out = dx if li == 0 else eng.dx_buf(li, nb)
                 eng.level_dgrad(eng.bwd[li], dy, nslots, out, nb, inv)
                 grad, layout = out, 1
         if side is not None:
             main.wait_stream(side)
+
+    def level_param_grads(self, li: int, nb: int, grad: torch.Tensor, layout: int, am_l: torch.Tensor, src: torch.Tensor,
+                          src_is_pixels: bool, src_plane_slots: int, sc, inv, g_w: torch.Tensor, g_b: torch.Tensor) -> None:
+        """The parameter side of level ``li`` on the current stream: bias and weight gradient of its ``nb`` clips from the POOLED
+        gradient ``grad`` (``layout`` / arg-max bytes ``am_l`` as vd_unpool_relu_bwd takes them) and the level's source ``src``
+        (fp32 pixels (nb,T,3,H,W), or channels-last slots with ``src_plane_slots`` per plane), ACCUMULATED into g_w / g_b.
+        ``sc`` / ``inv``: the power-of-two scale of ``level_unpool`` for this gradient and its inverse (None: bf16 formats)."""
+        eng = self.eng
+        cout, To, Ho, Wo, pt = eng.dims[li][1], *eng.dims[li][8:12]
+        # bias gradient from the pooled gradient (the dense dy has one non-zero per live pool window)
+        if hip.deterministic():
+            nsc = int(hip.lib().vd_bias_grad_pooled_scratch_floats(nb, cout, To * Ho * Wo))
+            bsc = eng._buf("bias_part%d" % li, (nsc,), torch.float32)
+            hip.run("vd_bias_grad_pooled_ordered", hip.ptr(grad), hip.ptr(am_l), nb, cout, To * Ho * Wo, layout,
+                    hip.ptr(bsc), hip.ptr(g_b), hip.stream_ptr(self.device))
+        else:
+            hip.run("vd_bias_grad_pooled", hip.ptr(grad), hip.ptr(am_l), nb, cout, To * Ho * Wo, layout,
+                    hip.ptr(g_b), hip.stream_ptr(self.device))
+        op = self._wgrad(li, nb)
+        # pooled gradient -> packed B operand of the weight-gradient program in one pass (4-8x fewer bytes than
+        # re-reading the dense slots, which for the first layer are not even written when nobody else needs them)
+        op.run_pooled(src, src_is_pixels, src_plane_slots, grad, am_l, layout, (To, Ho, Wo, pt), sc, g_w, out_scale=inv)
 
     def _side_stream(self):
         if getattr(self, "_side", None) is None:
