@@ -296,6 +296,46 @@ def test_no_seed_record_where_nothing_is_evaluated(driver, files, monkeypatch):
     assert _tree(save) == _files_of(driver, (0,), best=False)
 
 
+# ---- run_dm's three --memories modes side by side ---------------------------------------------------------------------------
+# 2 classes, 8 frames, 64x64, --Iteration 1 --eval_it 1 (evaluation iterations 0 and 1), --eval_ranks all --eval_seed 7, with
+# --no_eval and without it on data that has no test split.  The literals were recorded by running the commit BEFORE the three
+# modes shared one loop; they differ between the modes on purpose (run_dm's docstring): images and key frames write nothing under
+# --no_eval and log the seed whenever they may evaluate; static writes static_0.pt either way and logs no seed without test images.
+SEED_KEYS, LOSS_KEYS = ["eval_ranks", "eval_seed", "world"], ["Loss", "elapsed_s", "step"]
+THREE_MODES = {
+    ("images", "no_eval"): ([], [LOSS_KEYS, LOSS_KEYS]),
+    ("images", "no_test"): (["Baseline_DM/synthetic_ipc2_0.1/images_0.pt"], [SEED_KEYS, LOSS_KEYS, LOSS_KEYS]),
+    ("static", "no_eval"): (["Static_DM/synthetic_spc2_0.1/static_0.pt"], [LOSS_KEYS, LOSS_KEYS]),
+    ("static", "no_test"): (["Static_DM/synthetic_spc2_0.1/static_0.pt"], [LOSS_KEYS, LOSS_KEYS]),
+    ("keyframes", "no_eval"): ([], [LOSS_KEYS, LOSS_KEYS]),
+    ("keyframes", "no_test"): (["Keyframes_DM/synthetic_ipc2_k3_linear_0.1/keyframes_0.pt"], [SEED_KEYS, LOSS_KEYS, LOSS_KEYS]),
+}
+
+
+def _three_modes_run(memories, flavour, d):
+    """-> (files under --save_path, key sets of the log records in order, steps of the records that have one)."""
+    argv = ["--memories", memories, "--dataset", "synthetic", "--num_classes", "2", "--pool_per_class", "3", "--ipc", "2", "--spc", "2",
+            "--key_frames", "3", "--Iteration", "1", "--eval_it", "1", "--batch_real", "2", "--frames", str(T), "--im_size", str(HW),
+            "--lr_img", "0.1", "--num_eval", "1", "--save_path", str(d / "save"), "--eval_ranks", "all", "--eval_seed", "7"]
+    if memories == "static":          # (synthetic stills come with test images: a file of stills without any instead)
+        g = torch.Generator().manual_seed(5)
+        torch.save({"images": torch.randn(6, 3, HW, HW, generator=g), "labels": torch.arange(2).repeat(3)}, d / "stills.pt")
+        argv += ["--data_file", str(d / "stills.pt")]
+    log = []
+    run_dm.run(run_dm.build_parser().parse_args(argv + (["--no_eval"] if flavour == "no_eval" else [])), backend=OracleBackend(), log=log)
+    return _tree(str(d / "save")), [sorted(r) for r in log], [r["step"] for r in log if "step" in r]
+
+
+@pytest.mark.parametrize("memories,flavour", sorted(THREE_MODES))
+def test_run_dm_three_modes_files_and_records(memories, flavour, tmp_path, monkeypatch):
+    spy = Spy(monkeypatch)
+    files_want, keys_want = THREE_MODES[(memories, flavour)]
+    tree, keys, steps = _three_modes_run(memories, flavour, tmp_path)
+    assert tree == files_want
+    assert keys == keys_want and steps == [0, 1]
+    assert spy.pool == [] and spy.synset == [] and spy.networks == []          # nothing to evaluate with in either flavour
+
+
 @pytest.mark.parametrize("driver", DRIVERS)
 def test_eval_ranks_all_refuses_other_networks(driver, files, monkeypatch):
     spy = Spy(monkeypatch)

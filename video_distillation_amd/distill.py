@@ -130,6 +130,41 @@ def sample_real_indices(it: int, counts: Sequence[int], offsets: Sequence[int], 
     return np.concatenate(out).astype(np.int64) if out else np.zeros(0, dtype=np.int64)
 
 
+def init_real_rows(pool, classes: Sequence[int], per: int) -> torch.Tensor:
+    """``--init real`` (distill_baseline.py:96-100): the pool rows of the first ``per`` items of every class in ``classes``, class
+    after class (a class with fewer repeats them cyclically), as an index on the pool's device."""
+    idx = np.concatenate([pool.offsets[c] + np.arange(per) % pool.counts[c] for c in classes]) if len(classes) else np.zeros(0, dtype=np.int64)
+    return torch.as_tensor(idx, device=pool.clips.device, dtype=torch.int64)
+
+
+def check_pool_rows(who: str, pool, classes: Sequence[int]) -> None:
+    """Refuses (in the name of the trainer ``who``) a pool of stills that does not hold all rows of ``classes``: every index
+    ``sample_real_indices`` draws must lie in the pool, because the kernel that reads the stills does not check."""
+    n = pool.clips.shape[0]
+    for c in classes:
+        if pool.offsets[c] < 0 or pool.offsets[c] + pool.counts[c] > n:
+            raise ValueError("%s: class %d occupies rows %d..%d of a pool of %d stills" % (who, c, pool.offsets[c], pool.offsets[c] + pool.counts[c], n))
+
+
+def gather_rows(rows: torch.Tensor, per: int, owners: Sequence[Sequence[int]]) -> torch.Tensor:
+    """All ranks' memories in class order on every rank, in ONE all-gather.  ``rows`` is this rank's shard (``per`` rows per owned
+    class, in the order of its classes) and ``owners[r]`` the classes of rank ``r``'s shard in its order, the same list on every
+    rank.  The shards are padded to the largest (an all-gather takes equal sizes), gathered, cut back, and reordered where
+    the ranks' classes do not already follow each other (hybrid: the split classes sit behind each rank's block).  The caller
+    decides whether there is anything to gather (``collectives_on``) and waits for its own streams first."""
+    sizes = [len(o) * per for o in owners]
+    pad = torch.zeros((max(sizes),) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+    pad[:rows.shape[0]] = rows
+    parts = [torch.empty_like(pad) for _ in owners]
+    _all_gather(parts, pad)
+    out = torch.cat([p[:s] for p, s in zip(parts, sizes)], dim=0)
+    order = [c for o in owners for c in o]                    # class of every gathered block of ``per`` rows
+    if order != sorted(order):
+        pos = torch.as_tensor(np.argsort(order), device=out.device)
+        out = out.view(len(order), per, *out.shape[1:])[pos].reshape(out.shape)
+    return out
+
+
 def fresh_network_weights(seed: int, device) -> List[torch.Tensor]:
     """A fresh random ConvNet3D feature stack, drawn ON the device with PyTorch's default Conv3d
     distribution (kaiming-uniform a=sqrt(5) == U(+-1/sqrt(fan_in)) for weight and bias), from a
@@ -620,9 +655,7 @@ class DMTrainer:
             self.block, self.split, self.split_owned = hybrid_partition(num_classes, rank, world)
             self.classes = self.block + self.split_owned
         if image_syn is None:   # --init real (distill_baseline.py:96-100): first ipc real clips of each class
-            idx = np.concatenate([pool.offsets[c] + np.arange(ipc) % pool.counts[c] for c in self.classes]) \
-                if self.classes else np.zeros(0, dtype=np.int64)
-            image_syn = pool.clips[torch.as_tensor(idx, device=pool.clips.device, dtype=torch.int64)].clone()
+            image_syn = pool.clips[init_real_rows(pool, self.classes, ipc)].clone()
         self.image_syn = image_syn.contiguous()
         self.buf = torch.zeros_like(self.image_syn)
         self.steps_done = 0
@@ -867,25 +900,10 @@ class DMTrainer:
         """All synthetic clips in class order on every rank (evaluation / ``images_*.pt``).  Waits for the steps still
         in flight on the trainer's own streams first: with ``overlap=True`` the SGD write of the latest step may not have
         landed when the caller's stream starts copying."""
-        if hasattr(self, "sync"):
-            self.sync()
+        self.sync()
         if not collectives_on(self.world):
             return self.image_syn
-        import torch.distributed as dist
-        owners = [self.owned_classes(r) if hasattr(self, "owned_classes") else
-                  list(range(*class_range(self.num_classes, r, self.world))) for r in range(self.world)]
-        sizes = [len(o) * self.ipc for o in owners]
-        mx = max(sizes)
-        pad = torch.zeros((mx,) + tuple(self.image_syn.shape[1:]), dtype=self.image_syn.dtype, device=self.image_syn.device)
-        pad[:self.image_syn.shape[0]] = self.image_syn
-        parts = [torch.empty_like(pad) for _ in range(self.world)]
-        _all_gather(parts, pad)
-        out = torch.cat([p[:s] for p, s in zip(parts, sizes)], dim=0)
-        order = [c for o in owners for c in o]                    # class of every gathered block of ipc rows
-        if order != sorted(order):                                # (hybrid: the split classes sit behind each rank's block)
-            pos = torch.as_tensor(np.argsort(order), device=out.device)
-            out = out.view(len(order), self.ipc, *out.shape[1:])[pos].reshape(out.shape)
-        return out
+        return gather_rows(self.image_syn, self.ipc, [self.owned_classes(r) for r in range(self.world)])
 
 
 class S2DTrainer:
@@ -1033,15 +1051,9 @@ class S2DTrainer:
         shape_d = (-1, self.dpc) + tuple(self.dynamic.shape[1:])
         if not collectives_on(self.world):
             return self.static, self.dynamic.view(shape_d)
-        counts = [b - a for a, b in (class_range(self.num_classes, r, self.world) for r in range(self.world))]
-        out = []
-        for shard, per in ((self.static, self.spc), (self.dynamic, self.dpc)):
-            pad = torch.zeros((max(counts) * per,) + tuple(shard.shape[1:]), dtype=shard.dtype, device=shard.device)
-            pad[:shard.shape[0]] = shard
-            parts = [torch.empty_like(pad) for _ in range(self.world)]
-            _all_gather(parts, pad)
-            out.append(torch.cat([p[:c * per] for p, c in zip(parts, counts)], dim=0))      # class blocks are contiguous per rank
-        return out[0], out[1].view(shape_d)
+        owners = [range(*class_range(self.num_classes, r, self.world)) for r in range(self.world)]
+        static = gather_rows(self.static, self.spc, owners)          # (two collectives: the static rows first, then the dynamic ones)
+        return static, gather_rows(self.dynamic, self.dpc, owners).view(shape_d)
 
     def mark(self):
         ev = torch.cuda.Event(enable_timing=True)
@@ -1172,9 +1184,7 @@ class GMTrainer:
         self.c_lo, self.c_hi = class_range(num_classes, rank, world)
         self.classes = list(range(self.c_lo, self.c_hi))
         if image_syn is None:
-            idx = np.concatenate([pool.offsets[c] + np.arange(ipc) % pool.counts[c] for c in self.classes]) \
-                if self.classes else np.zeros(0, dtype=np.int64)
-            image_syn = pool.clips[torch.as_tensor(idx, device=pool.clips.device, dtype=torch.int64)].clone()
+            image_syn = pool.clips[init_real_rows(pool, self.classes, ipc)].clone()
         self.image_syn = image_syn.contiguous()
         self.buf = torch.zeros_like(self.image_syn)
         self.steps_done = 0
@@ -1284,7 +1294,12 @@ class GMTrainer:
             _all_reduce(local_loss)
         return local_loss
 
-    gather_syn = DMTrainer.gather_syn
+    def gather_syn(self) -> torch.Tensor:
+        """All synthetic clips in class order on every rank (the network's training steps, evaluation / ``images_*.pt``); this
+        trainer shards by whole-class blocks only."""
+        if not collectives_on(self.world):
+            return self.image_syn
+        return gather_rows(self.image_syn, self.ipc, [range(*class_range(self.num_classes, r, self.world)) for r in range(self.world)])
 
     # -- what differs between clips and still images (StillGMTrainer) ------------------------------------------------------
     def _real_batch(self, idx: torch.Tensor) -> torch.Tensor:
@@ -1341,14 +1356,9 @@ class StillGMTrainer(GMTrainer):
         if stills.dim() != 4 or tuple(stills.shape[1:]) != (3, geo.height, geo.width):
             raise ValueError("StillGMTrainer: a pool of stills (N, 3, %d, %d), not %s" % (geo.height, geo.width, tuple(stills.shape)))
         c_lo, c_hi = class_range(num_classes, rank, world)
-        for c in range(c_lo, c_hi):          # (every index sample_real_indices draws lies in the pool: the kernel does not check)
-            if pool.offsets[c] < 0 or pool.offsets[c] + pool.counts[c] > stills.shape[0]:
-                raise ValueError("StillGMTrainer: class %d occupies rows %d..%d of a pool of %d stills"
-                                 % (c, pool.offsets[c], pool.offsets[c] + pool.counts[c], stills.shape[0]))
+        check_pool_rows("StillGMTrainer", pool, range(c_lo, c_hi))
         if static is None:          # --init real: the first spc stills of each owned class
-            idx = np.concatenate([pool.offsets[c] + np.arange(spc) % pool.counts[c] for c in range(c_lo, c_hi)]) \
-                if c_hi > c_lo else np.zeros(0, dtype=np.int64)
-            static = stills[torch.as_tensor(idx, device=stills.device, dtype=torch.int64)].clone()
+            static = stills[init_real_rows(pool, range(c_lo, c_hi), spc)].clone()
         if tuple(static.shape) != ((c_hi - c_lo) * spc, 3, geo.height, geo.width):
             raise ValueError("StillGMTrainer: static %s for %d owned classes x spc %d" % (tuple(static.shape), c_hi - c_lo, spc))
         self.static = static.contiguous()
@@ -1371,12 +1381,54 @@ class StillGMTrainer(GMTrainer):
         of the s2d stage reads (``static_*.pt``)."""
         if not collectives_on(self.world):
             return self.static
-        import types
-        return DMTrainer.gather_syn(types.SimpleNamespace(world=self.world, num_classes=self.num_classes, ipc=self.spc,
-                                                          image_syn=self.static))
+        return gather_rows(self.static, self.spc, [range(*class_range(self.num_classes, r, self.world)) for r in range(self.world)])
 
 
-class StillDMTrainer(DMTrainer):
+class MemoryDMTrainer(DMTrainer):
+    """Distribution matching where the learned memory is NOT the synthetic clip: ``memory`` (``per`` rows per owned class, with a
+    momentum buffer of its shape) is expanded to ``image_syn``, the clips ``DMTrainer.step`` embeds.  A subclass checks its pool,
+    cuts its initial memory from it, hands it over (``_set_memory``) and says how a memory becomes clips and a clip gradient a
+    memory gradient (``_expand`` / ``_reduce``); what follows from that is here, all of it on the synthetic-clip stream."""
+
+    def __init__(self, backend, pool: RealPool, geo: P.NetGeometry, num_classes: int, per: int, batch_real: int, lr_img: float,
+                 momentum: float, rank: int, world: int, shard: str, exchange: str):
+        who = type(self).__name__
+        if exchange != "owner":
+            raise ValueError("%s: exchange=%r is a benchmark leg of the clip trainer; %s is owner-computes" % (who, exchange, who))
+        self.geo = geo
+        # the base class decides the sharding (``shard``, ``classes``, ``block`` / ``split``) on an empty memory; the memory, its
+        # momentum and the clips follow in ``_set_memory``, once the subclass knows the classes this rank owns and reads
+        super().__init__(backend, pool, num_classes, per, batch_real, lr_img, momentum=momentum, rank=rank, world=world,
+                         image_syn=pool.clips[:0], shard=shard, exchange=exchange)
+
+    def _set_memory(self, memory: torch.Tensor) -> None:
+        self.memory = memory.contiguous()
+        self.buf = torch.zeros_like(self.memory)          # momentum of the MEMORY, not of the clips
+        self.image_syn = self._expanded()
+
+    def _expanded(self) -> torch.Tensor:
+        """``_expand(memory)`` as a fresh tensor that the synthetic-clip stream may read."""
+        x = self._expand(self.memory)
+        if getattr(self.be, "two_streams", False):
+            x.record_stream(self.be.s_syn)
+        return x
+
+    def _apply_pixel_grad(self, grad: torch.Tensor, first: bool) -> None:
+        """Reduce, SGD with momentum on ``memory``, expand again for the next step: all three in here, so that ``step(it,
+        overlap=True)`` and the deferred backward keep their order (SGD(i) and the expansion precede the forward of step i + 1)."""
+        self.be.sgd(self.memory, self.buf, self._reduce(grad), self.lr_img, self.momentum, first=first)
+        self.image_syn = self._expanded()
+
+    def gather_memory(self) -> torch.Tensor:
+        """All ranks' memories in class order on every rank: row ``c*ipc + j`` (what the mode's file holds), after the steps in
+        flight.  ``gather_static`` / ``gather_keys`` are this method."""
+        self.sync()
+        if not collectives_on(self.world):
+            return self.memory
+        return gather_rows(self.memory, self.ipc, [self.owned_classes(r) for r in range(self.world)])
+
+
+class StillDMTrainer(MemoryDMTrainer):
     """Distribution matching on STILL clips: the static-learning stage of the static + dynamic method on the DM loop
     (``StillGMTrainer`` is the same stage on gradient matching).  The memories are ``static`` (n_owned*spc, 3, H, W) images
     with a momentum buffer of that shape; ``pool.clips`` holds stills (N, 3, H, W).
@@ -1395,38 +1447,28 @@ class StillDMTrainer(DMTrainer):
     def __init__(self, backend, pool: RealPool, geo: P.NetGeometry, num_classes: int, spc: int, batch_real: int, lr_img: float,
                  momentum: float = 0.5, rank: int = 0, world: int = 1, static: Optional[torch.Tensor] = None,
                  shard: str = "class", exchange: str = "owner"):
-        if exchange != "owner":
-            raise ValueError("StillDMTrainer: exchange=%r is a benchmark leg of the clip trainer; the still trainer is owner-computes" % (exchange,))
         stills = pool.clips
         if stills.dim() != 4 or tuple(stills.shape[1:]) != (3, geo.height, geo.width):
             raise ValueError("StillDMTrainer: a pool of stills (N, 3, %d, %d), not %s" % (geo.height, geo.width, tuple(stills.shape)))
-        self.geo, self.spc = geo, int(spc)
-        # the base class decides the sharding (``shard``, ``classes``, ``block`` / ``split``) on an empty memory; the images, their
-        # momentum and the clips follow below, once the classes this rank owns and reads are known
-        super().__init__(backend, pool, num_classes, spc, batch_real, lr_img, momentum=momentum, rank=rank, world=world,
-                         image_syn=stills[:0], shard=shard, exchange=exchange)
+        self.spc = int(spc)
+        super().__init__(backend, pool, geo, num_classes, spc, batch_real, lr_img, momentum, rank, world, shard, exchange)
         owned = self.classes
-        read = list(range(num_classes)) if self.shard == "batch" else (self.block + self.split if self.shard == "hybrid" else owned)
-        for c in read:          # (every index sample_real_indices draws lies in the pool: the kernel does not check)
-            if pool.offsets[c] < 0 or pool.offsets[c] + pool.counts[c] > stills.shape[0]:
-                raise ValueError("StillDMTrainer: class %d occupies rows %d..%d of a pool of %d stills"
-                                 % (c, pool.offsets[c], pool.offsets[c] + pool.counts[c], stills.shape[0]))
+        # the classes this rank READS: all of them under 'batch', its block and every split class under 'hybrid'
+        check_pool_rows("StillDMTrainer", pool, range(num_classes) if self.shard == "batch" else
+                        (self.block + self.split if self.shard == "hybrid" else owned))
         if static is None:          # --init real: the first spc stills of each owned class
-            idx = np.concatenate([pool.offsets[c] + np.arange(spc) % pool.counts[c] for c in owned]) if owned \
-                else np.zeros(0, dtype=np.int64)
-            static = stills[torch.as_tensor(idx, device=stills.device, dtype=torch.int64)].clone()
+            static = stills[init_real_rows(pool, owned, spc)].clone()
         if tuple(static.shape) != (len(owned) * spc, 3, geo.height, geo.width):
             raise ValueError("StillDMTrainer: static %s for %d owned classes x spc %d" % (tuple(static.shape), len(owned), spc))
-        self.static = static.contiguous()
-        self.buf = torch.zeros_like(self.static)          # momentum of the IMAGES
-        self.image_syn = self._expand_static()
+        self._set_memory(static)
 
-    def _expand_static(self) -> torch.Tensor:
-        """``still_expand(static)`` as a fresh tensor that the synthetic-clip stream may read."""
-        x = still_expand(self.be, self.static, None, self.geo.frames)
-        if getattr(self.be, "two_streams", False):
-            x.record_stream(self.be.s_syn)
-        return x
+    static = property(lambda self: self.memory)          # (the same tensor: SGD steps it in place)
+
+    def _expand(self, static: torch.Tensor) -> torch.Tensor:
+        return still_expand(self.be, static, None, self.geo.frames)
+
+    def _reduce(self, grad: torch.Tensor) -> torch.Tensor:
+        return still_reduce(self.be, grad)
 
     def _embed_real(self, idx_t: torch.Tensor, segments=None) -> torch.Tensor:
         be = self.be
@@ -1437,19 +1479,7 @@ class StillDMTrainer(DMTrainer):
         clips = still_expand(be, self.pool.clips, idx_t, self.geo.frames)
         return be.embed_pool(clips, torch.arange(clips.shape[0], device=clips.device))
 
-    def _apply_pixel_grad(self, grad: torch.Tensor, first: bool) -> None:
-        be = self.be
-        be.sgd(self.static, self.buf, still_reduce(be, grad), self.lr_img, self.momentum, first=first)
-        self.image_syn = self._expand_static()          # the clips of the next step
-
-    def gather_static(self) -> torch.Tensor:
-        """All ranks' images in class order on every rank: row ``c*spc + j`` (``static_*.pt``), after the steps in flight."""
-        self.sync()
-        if not collectives_on(self.world):
-            return self.static
-        import types
-        return DMTrainer.gather_syn(types.SimpleNamespace(world=self.world, num_classes=self.num_classes, ipc=self.spc,
-                                                          image_syn=self.static, owned_classes=self.owned_classes))
+    gather_static = MemoryDMTrainer.gather_memory          # (``static_*.pt``: row ``c*spc + j``)
 
 
 def keyframe_expand(be, keys: torch.Tensor, table) -> torch.Tensor:
@@ -1470,7 +1500,7 @@ def keyframe_reduce(be, g: torch.Tensor, table) -> torch.Tensor:
     return keyframes.reduce_torch(g, table)
 
 
-class KeyframeDMTrainer(DMTrainer):
+class KeyframeDMTrainer(MemoryDMTrainer):
     """Distribution matching on KEY-FRAME memories: each memory is ``K`` learned frames, ``keys`` (n_owned*ipc, K, 3, H, W) with a
     momentum buffer of that shape, brought to the network's T frames by a fixed two-tap table (``keyframes.table(T, K, interp)``:
     the paper's segments for ``'nearest'``, linear interpolation with aligned end points for ``'linear'``).  K = 1 is the still
@@ -1489,50 +1519,30 @@ class KeyframeDMTrainer(DMTrainer):
                  key_frames: int = 4, interp: str = "linear", momentum: float = 0.5, rank: int = 0, world: int = 1,
                  keys: Optional[torch.Tensor] = None, shard: str = "class", exchange: str = "owner"):
         from . import keyframes
-        if exchange != "owner":
-            raise ValueError("KeyframeDMTrainer: exchange=%r is a benchmark leg of the clip trainer; the key-frame trainer is owner-computes" % (exchange,))
         clips = pool.clips
         if clips.dim() != 5 or tuple(clips.shape[1:]) != (geo.frames, 3, geo.height, geo.width):
             raise ValueError("KeyframeDMTrainer: a pool of clips (N, %d, 3, %d, %d), not %s" % (geo.frames, geo.height, geo.width, tuple(clips.shape)))
-        self.geo, self.table = geo, keyframes.table(geo.frames, key_frames, interp)
+        self.table = keyframes.table(geo.frames, key_frames, interp)
         self.key_frames, self.interp = int(key_frames), interp
-        # the base class decides the sharding on an empty memory; the keys, their momentum and the clips follow once the classes
-        # this rank owns are known
-        super().__init__(backend, pool, num_classes, ipc, batch_real, lr_img, momentum=momentum, rank=rank, world=world,
-                         image_syn=clips[:0], shard=shard, exchange=exchange)
+        super().__init__(backend, pool, geo, num_classes, ipc, batch_real, lr_img, momentum, rank, world, shard, exchange)
         owned = self.classes
         if keys is None:          # --init real: the first ipc clips of each owned class, key k from frame init_frames[k]
-            idx = np.concatenate([pool.offsets[c] + np.arange(ipc) % pool.counts[c] for c in owned]) if owned \
-                else np.zeros(0, dtype=np.int64)
             frames = torch.as_tensor(keyframes.init_frames(geo.frames, self.key_frames, interp), device=clips.device, dtype=torch.int64)
-            keys = clips[torch.as_tensor(idx, device=clips.device, dtype=torch.int64)].index_select(1, frames).clone()
+            keys = clips[init_real_rows(pool, owned, ipc)].index_select(1, frames).clone()
         if tuple(keys.shape) != (len(owned) * ipc, self.key_frames, 3, geo.height, geo.width):
             raise ValueError("KeyframeDMTrainer: keys %s for %d owned classes x ipc %d x %d key frames"
                              % (tuple(keys.shape), len(owned), ipc, self.key_frames))
-        self.keys = keys.contiguous()
-        self.buf = torch.zeros_like(self.keys)          # momentum of the KEYS
-        self.image_syn = self._expand_keys()
+        self._set_memory(keys)
 
-    def _expand_keys(self) -> torch.Tensor:
-        """``keyframe_expand(keys)`` as a fresh tensor that the synthetic-clip stream may read."""
-        x = keyframe_expand(self.be, self.keys, self.table)
-        if getattr(self.be, "two_streams", False):
-            x.record_stream(self.be.s_syn)
-        return x
+    keys = property(lambda self: self.memory)          # (the same tensor: SGD steps it in place)
 
-    def _apply_pixel_grad(self, grad: torch.Tensor, first: bool) -> None:
-        be = self.be
-        be.sgd(self.keys, self.buf, keyframe_reduce(be, grad, self.table), self.lr_img, self.momentum, first=first)
-        self.image_syn = self._expand_keys()          # the clips of the next step
+    def _expand(self, keys: torch.Tensor) -> torch.Tensor:
+        return keyframe_expand(self.be, keys, self.table)
 
-    def gather_keys(self) -> torch.Tensor:
-        """All ranks' keys in class order on every rank: row ``c*ipc + j`` (``keyframes_*.pt``), after the steps in flight."""
-        self.sync()
-        if not collectives_on(self.world):
-            return self.keys
-        import types
-        return DMTrainer.gather_syn(types.SimpleNamespace(world=self.world, num_classes=self.num_classes, ipc=self.ipc,
-                                                          image_syn=self.keys, owned_classes=self.owned_classes))
+    def _reduce(self, grad: torch.Tensor) -> torch.Tensor:
+        return keyframe_reduce(self.be, grad, self.table)
+
+    gather_keys = MemoryDMTrainer.gather_memory          # (``keyframes_*.pt``: row ``c*ipc + j``)
 
 
 # ------------------------------------------------------------------------------------------------

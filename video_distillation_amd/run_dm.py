@@ -115,41 +115,93 @@ def load_data(args, rank, world, geo, device):
     return pool, num_classes, (c_lo, c_hi), driver.file_test_loader(blob)
 
 
-def run_static(args, backend=None, log=None, shard: str = "class", exchange: str = "owner"):
-    """``--memories static``: the loop of ``run`` on ``distill.StillDMTrainer``."""
-    from . import checkpoint, distill, plan, utils
-    from .run_dc import StillTestLoader, load_stills
-    if args.spc < 1:
+def run(args, backend=None, log=None, shard: str = "class", exchange: str = "owner"):
+    """``--memories`` decides the set-up -- data, trainer, ``per_class``, ``gather``, ``save`` and ``like_run_dc`` -- and nothing in
+    the loop below it, which serves all three modes."""
+    from . import checkpoint, distill, keyframes, plan, utils
+    memories = getattr(args, 'memories', 'images')
+    # the refusals that need no data, before any is loaded
+    if memories == 'static' and args.spc < 1:
         raise ValueError("--spc %d: at least one memory per class" % args.spc)
+    if memories == 'keyframes':
+        keyframes.table(args.frames, args.key_frames, args.interp)
     rank, world, device = driver.start(use_cuda=backend is None)
     geo = plan.NetGeometry(args.frames, args.im_size, args.im_size)
-    pool, num_classes, (c_lo, c_hi), testloader = load_stills(args, rank, world, device)
+    if memories == 'static':
+        from .run_dc import StillTestLoader, load_stills
+        pool, num_classes, (c_lo, c_hi), testloader = load_stills(args, rank, world, device)
+    else:
+        pool, num_classes, (c_lo, c_hi), testloader = load_data(args, rank, world, geo, device)
     if backend is None:
         backend = distill.HipBackend(geo, device, prec_real=args.prec_real, prec_syn=args.prec_syn)
-    if testloader is not None:
-        testloader = StillTestLoader(testloader, backend, device, args.frames)
-    static = None
-    if args.init == 'noise':
-        gen = torch.Generator().manual_seed(args.seed)          # drawn in full on the host: every sharding starts from the same state
-        static = torch.randn((num_classes * args.spc, 3, args.im_size, args.im_size), generator=gen)[c_lo * args.spc:c_hi * args.spc].to(device)
-    trainer = distill.StillDMTrainer(backend, pool, geo, num_classes, args.spc, args.batch_real, args.lr_img, momentum=0.5,
-                                     rank=rank, world=world, static=static, shard=shard, exchange=exchange)
+    common = dict(momentum=0.5, rank=rank, world=world, shard=shard, exchange=exchange)
+    hw = (3, args.im_size, args.im_size)
+
+    def host_noise(per, *item):
+        """``--init noise`` of the static and key-frame modes: drawn in full on the host from ``--seed``, so that every sharding
+        starts from the same state, then the rows of this rank's memories (``DMTrainer.owned_classes``).  INTENDED to differ from
+        the images mode, which draws its own rows on the device from ``4321 + rank``."""
+        if args.init != 'noise':
+            return None
+        owned = list(range(c_lo, c_hi))
+        if shard == "hybrid" and world > 1:
+            block, _, split_owned = distill.hybrid_partition(num_classes, rank, world)
+            owned = block + split_owned
+        full = torch.randn((num_classes * per,) + item, generator=torch.Generator().manual_seed(args.seed))
+        return full[[c * per + j for c in owned for j in range(per)]].to(device)
+
+    # gather: () -> (all synthetic clips, all memories as the mode's file holds them), collectives on every rank;
+    # save: (it, memories, best) -> the mode's file(s) of iteration ``it``
+    like_run_dc = memories == 'static'
+    per_class = args.spc if like_run_dc else args.ipc
+    if memories == 'static':
+        if testloader is not None:
+            testloader = StillTestLoader(testloader, backend, device, args.frames)
+        trainer = distill.StillDMTrainer(backend, pool, geo, num_classes, args.spc, args.batch_real, args.lr_img,
+                                         static=host_noise(args.spc, *hw), **common)
+        save_dir = os.path.join(args.save_path, "Static_DM", "%s_spc%d_%s" % (args.dataset, args.spc, args.lr_img))
+        gather = lambda: (trainer.gather_syn(), trainer.gather_static())
+        save = lambda it, static, best: checkpoint.save_static(save_dir, it, static, best=best)
+    elif memories == 'keyframes':
+        K = args.key_frames
+        trainer = distill.KeyframeDMTrainer(backend, pool, geo, num_classes, args.ipc, args.batch_real, args.lr_img, key_frames=K,
+                                            interp=args.interp, keys=host_noise(args.ipc, K, *hw), **common)
+        save_dir = os.path.join(args.save_path, "Keyframes_DM", "%s_ipc%d_k%d_%s_%s" % (args.dataset, args.ipc, K, args.interp, args.lr_img))
+        gather = lambda: (trainer.gather_syn(), trainer.gather_keys())
+        save = lambda it, keys, best: checkpoint.save_keyframes(save_dir, it, keys, args.interp, args.frames, best=best)
+    else:
+        image_syn = None
+        if args.init == 'noise':
+            gen = torch.Generator(device=device); gen.manual_seed(4321 + rank)
+            image_syn = torch.randn((c_hi - c_lo) * args.ipc, args.frames, *hw, device=device, generator=gen)
+        trainer = distill.DMTrainer(backend, pool, num_classes, args.ipc, args.batch_real, args.lr_img, image_syn=image_syn, **common)
+        save_dir = os.path.join(args.save_path, "Baseline_DM", "%s_ipc%d_%s" % (args.dataset, args.ipc, args.lr_img))
+        gather = lambda: (trainer.gather_syn(),) * 2          # (the clips are the memories)
+        save = lambda it, images, best: checkpoint.save_images(save_dir, it, images, best=best)
+
     eval_pool = utils.get_eval_pool(args.eval_mode, args.model, args.model)
     best_acc = {m: 0.0 for m in eval_pool}; best_std = {m: 0.0 for m in eval_pool}
-    save_dir = os.path.join(args.save_path, "Static_DM", "%s_spc%d_%s" % (args.dataset, args.spc, args.lr_img))
     log = driver.JsonLog(args.log_file, rank, log)
     evaluate = not args.no_eval and testloader is not None
+    # Two cadences, both INTENDED.  Images and key frames: a round (the gathers; a file at a new best or a multiple of 1000) at every
+    # evaluation iteration unless --no_eval, with or without test clips, and the seed is drawn and logged on the same condition;
+    # --no_eval writes nothing.  Static is run_dc --memories static's: rounds and seed only where something is evaluated, but the
+    # evaluation iterations that are multiples of 1000 write their file regardless -- the file is that stage's product.
+    rounds = evaluate if like_run_dc else not args.no_eval
     eval_seed = None
-    if args.eval_ranks == 'all' and evaluate:
+    if args.eval_ranks == 'all' and rounds:
         eval_seed = driver.draw_eval_seed(args.eval_seed, rank, world)
         log.emit({"eval_ranks": "all", "eval_seed": eval_seed, "world": world})
-    label_syn = torch.arange(num_classes).repeat_interleave(args.spc)
+    label_syn = torch.arange(num_classes).repeat_interleave(per_class)
     eval_its = set(np.arange(0, args.Iteration + 1, args.eval_it).tolist())
     t0 = time.time()
     for it in range(args.Iteration + 1):
-        if it in eval_its and (evaluate or it % 1000 == 0):          # (as run_dc: an unevaluated run still leaves its files)
-            syn_all = trainer.gather_syn()          # (collectives: every rank, whoever evaluates or saves)
-            static_all = trainer.gather_static()
+        if it in eval_its and (rounds or (like_run_dc and it % 1000 == 0)):
+            syn_all, memory_all = gather()
+            if not like_run_dc:
+                # INTENDED (run_dc has none): the gathers have waited already, but on a c8 two-stream backend every sync() counts
+                # towards VD_RANGE_CHECK_EVERY, so this one decides when the real side's range is read
+                trainer.sync()
             save_best = False
             if evaluate:
                 save_best, pooled = driver.evaluate_round(
@@ -160,117 +212,7 @@ def run_static(args, backend=None, log=None, shard: str = "class", exchange: str
                     log.emit({"step": it, "eval_pool": {"train_s": got["times"]["train_s"], "test_pass_s": got["times"]["test_pass_s"],
                                                         "assignment": got["assignment"]}})
             if rank == 0 and (save_best or it % 1000 == 0):
-                checkpoint.save_static(save_dir, it, static_all, best=save_best)
-        loss = trainer.global_loss(trainer.step(it, overlap=True))
-        if it % 10 == 0 or it == args.Iteration:
-            trainer.sync()
-            log.emit({"step": it, "Loss": float(loss) / num_classes, "elapsed_s": round(time.time() - t0, 3)})
-    trainer.sync()
-    log.close()
-    return trainer
-
-
-def run_keyframes(args, backend=None, log=None, shard: str = "class", exchange: str = "owner"):
-    """``--memories keyframes``: the loop of ``run`` on ``distill.KeyframeDMTrainer``."""
-    from . import checkpoint, distill, keyframes, plan, utils
-    K, T = args.key_frames, args.frames
-    keyframes.table(T, K, args.interp)          # (the refusals, before any data is loaded)
-    rank, world, device = driver.start(use_cuda=backend is None)
-    geo = plan.NetGeometry(T, args.im_size, args.im_size)
-    pool, num_classes, (c_lo, c_hi), testloader = load_data(args, rank, world, geo, device)
-    if backend is None:
-        backend = distill.HipBackend(geo, device, prec_real=args.prec_real, prec_syn=args.prec_syn)
-    keys = None
-    if args.init == 'noise':
-        gen = torch.Generator().manual_seed(args.seed)          # drawn in full on the host: every sharding starts from the same state
-        keys = torch.randn((num_classes * args.ipc, K, 3, args.im_size, args.im_size), generator=gen)
-        owned = list(range(c_lo, c_hi))
-        if shard == "hybrid" and world > 1:          # (the rows of a rank's memories: DMTrainer.owned_classes)
-            block, _, split_owned = distill.hybrid_partition(num_classes, rank, world)
-            owned = block + split_owned
-        rows = [c * args.ipc + j for c in owned for j in range(args.ipc)]
-        keys = keys[rows].to(device)
-    trainer = distill.KeyframeDMTrainer(backend, pool, geo, num_classes, args.ipc, args.batch_real, args.lr_img, key_frames=K,
-                                        interp=args.interp, momentum=0.5, rank=rank, world=world, keys=keys, shard=shard, exchange=exchange)
-    eval_pool = utils.get_eval_pool(args.eval_mode, args.model, args.model)
-    best_acc = {m: 0.0 for m in eval_pool}; best_std = {m: 0.0 for m in eval_pool}
-    save_dir = os.path.join(args.save_path, "Keyframes_DM", "%s_ipc%d_k%d_%s_%s" % (args.dataset, args.ipc, K, args.interp, args.lr_img))
-    log = driver.JsonLog(args.log_file, rank, log)
-    eval_seed = None
-    if args.eval_ranks == 'all' and not args.no_eval:
-        eval_seed = driver.draw_eval_seed(args.eval_seed, rank, world)
-        log.emit({"eval_ranks": "all", "eval_seed": eval_seed, "world": world})
-    label_syn = torch.arange(num_classes).repeat_interleave(args.ipc)
-    eval_its = set(np.arange(0, args.Iteration + 1, args.eval_it).tolist())
-    t0 = time.time()
-    for it in range(args.Iteration + 1):
-        if it in eval_its and not args.no_eval:
-            syn_all = trainer.gather_syn()          # (collectives: every rank, whoever evaluates or saves)
-            keys_all = trainer.gather_keys()
-            trainer.sync()
-            save_best = False
-            if testloader is not None:
-                save_best, pooled = driver.evaluate_round(
-                    args, it, syn_all.detach().clone(), label_syn, 'none', args.lr_net, testloader, eval_pool, best_acc, best_std, log,
-                    rank=rank, world=world, device=device, num_classes=num_classes,
-                    pool_seed=None if eval_seed is None else eval_seed + it)
-                for got in pooled:
-                    log.emit({"step": it, "eval_pool": {"train_s": got["times"]["train_s"], "test_pass_s": got["times"]["test_pass_s"],
-                                                        "assignment": got["assignment"]}})
-            if rank == 0 and (save_best or it % 1000 == 0):
-                checkpoint.save_keyframes(save_dir, it, keys_all, args.interp, T, best=save_best)
-        loss = trainer.global_loss(trainer.step(it, overlap=True))
-        if it % 10 == 0 or it == args.Iteration:
-            trainer.sync()
-            log.emit({"step": it, "Loss": float(loss) / num_classes, "elapsed_s": round(time.time() - t0, 3)})
-    trainer.sync()
-    log.close()
-    return trainer
-
-
-def run(args, backend=None, log=None, shard: str = "class", exchange: str = "owner"):
-    from . import checkpoint, distill, plan, utils
-    if getattr(args, 'memories', 'images') == 'static':
-        return run_static(args, backend, log, shard=shard, exchange=exchange)
-    if getattr(args, 'memories', 'images') == 'keyframes':
-        return run_keyframes(args, backend, log, shard=shard, exchange=exchange)
-    rank, world, device = driver.start(use_cuda=backend is None)
-    geo = plan.NetGeometry(args.frames, args.im_size, args.im_size)
-    pool, num_classes, (c_lo, c_hi), testloader = load_data(args, rank, world, geo, device)
-    if backend is None:
-        backend = distill.HipBackend(geo, device, prec_real=args.prec_real, prec_syn=args.prec_syn)
-    image_syn = None
-    if args.init == 'noise':
-        gen = torch.Generator(device=device); gen.manual_seed(4321 + rank)
-        image_syn = torch.randn((c_hi - c_lo) * args.ipc, args.frames, 3, args.im_size, args.im_size, device=device, generator=gen)
-    trainer = distill.DMTrainer(backend, pool, num_classes, args.ipc, args.batch_real, args.lr_img, momentum=0.5,
-                                rank=rank, world=world, image_syn=image_syn, shard=shard, exchange=exchange)
-    eval_pool = utils.get_eval_pool(args.eval_mode, args.model, args.model)
-    best_acc = {m: 0.0 for m in eval_pool}; best_std = {m: 0.0 for m in eval_pool}
-    save_dir = os.path.join(args.save_path, "Baseline_DM", "%s_ipc%d_%s" % (args.dataset, args.ipc, args.lr_img))
-    log = driver.JsonLog(args.log_file, rank, log)
-    eval_seed = None
-    if args.eval_ranks == 'all' and not args.no_eval:          # (drawn and logged whether or not the data has test clips)
-        eval_seed = driver.draw_eval_seed(args.eval_seed, rank, world)
-        log.emit({"eval_ranks": "all", "eval_seed": eval_seed, "world": world})
-    label_syn = torch.arange(num_classes).repeat_interleave(args.ipc)
-    eval_its = set(np.arange(0, args.Iteration + 1, args.eval_it).tolist())
-    t0 = time.time()
-    for it in range(args.Iteration + 1):
-        if it in eval_its and not args.no_eval:
-            syn_all = trainer.gather_syn()
-            trainer.sync()
-            save_best = False
-            if testloader is not None:
-                save_best, pooled = driver.evaluate_round(
-                    args, it, syn_all.detach().clone(), label_syn, 'none', args.lr_net, testloader, eval_pool, best_acc, best_std, log,
-                    rank=rank, world=world, device=device, num_classes=num_classes,
-                    pool_seed=None if eval_seed is None else eval_seed + it)
-                for got in pooled:
-                    log.emit({"step": it, "eval_pool": {"train_s": got["times"]["train_s"], "test_pass_s": got["times"]["test_pass_s"],
-                                                        "assignment": got["assignment"]}})
-            if rank == 0 and (save_best or it % 1000 == 0):
-                checkpoint.save_images(save_dir, it, syn_all, best=save_best)
+                save(it, memory_all, save_best)
         loss = trainer.global_loss(trainer.step(it, overlap=True))
         if it % 10 == 0 or it == args.Iteration:
             trainer.sync()
