@@ -9,7 +9,7 @@ is written into the repo except input/output TENSORS of its functions.
 Usage:  python tools/gen_golden.py            # rewrites tests/golden/*.npz
 Fixtures follow SURVEY.md section 8(c): G1 layer-wise fwd, G2 DM class term, G3 DM step x2,
 G4 hallucinator, G5 s2d DM step, G6 match_loss KATs, G7 evaluate_synset/epoch, G8 is G3
-re-used by the sharding tests.
+re-used by the sharding tests; G18 FRePo's kernel ridge predictor (tests/golden/nfr/values.npz).
 """
 import contextlib
 import io
@@ -845,6 +845,63 @@ def g16(networks, utils):
         noise_test=noise_test, problem_seed=1606, train_checksum=np.array(checksum(train_x)), test_checksum=np.array(checksum(test_x)), **out)
 
 
+def g18():
+    """FRePo's kernel ridge predictor: ``PoolElement.nfr`` of FRePo/script/distill_s2d.py, imported, on DOUBLE inputs with a
+    stand-in model whose ``embed`` returns its input (so x is the feature matrix), and the gradient of sum(pred * g_pred) by its
+    own autograd.  The script's top-level imports that are absent here get empty stub modules (``wandb``; ``torchvision`` is
+    stubbed by ``import_reference``).  Inputs are the seeded cases of tests/nfr_oracle.py; tensors only."""
+    frepo = os.path.join(REF, "FRePo")
+    for path in (os.path.join(frepo, "script"), frepo):
+        sys.path.insert(0, path)
+    for name in ("wandb", "matplotlib", "matplotlib.pyplot", "scipy.ndimage.interpolation", "torch._vmap_internals"):
+        try:
+            __import__(name)
+        except Exception:
+            sys.modules[name] = types.ModuleType(name)
+            if name == "scipy.ndimage.interpolation":
+                sys.modules[name].rotate = None
+            if name == "torch._vmap_internals":
+                sys.modules[name].vmap = lambda f: f
+    try:
+        import lib_torch.utils  # noqa: F401
+    except ImportError:
+        # FRePo/lib_torch/utils.py asks lib_torch/networks.py for names that file does not define, so it cannot be imported at
+        # all; PoolElement.nfr uses none of the six names the script takes from it
+        for name in [k for k in sys.modules if k == "lib_torch" or k.startswith("lib_torch.")]:
+            del sys.modules[name]
+        pkg, stub = types.ModuleType("lib_torch"), types.ModuleType("lib_torch.utils")
+        pkg.__path__ = []
+        for name in ("get_network", "evaluate_synset", "get_dataset", "get_eval_pool", "HallucinatorSharedDataset", "Conv3DNet"):
+            setattr(stub, name, None)
+        pkg.utils = stub
+        sys.modules["lib_torch"], sys.modules["lib_torch.utils"] = pkg, stub
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tests import nfr_oracle as O
+    with contextlib.redirect_stdout(io.StringIO()):
+        import distill_s2d
+
+    class Identity(torch.nn.Module):
+        def embed(self, x):
+            return x
+
+    pe = distill_s2d.PoolElement.__new__(distill_s2d.PoolElement)       # (its __init__ builds a network and an optimiser)
+    pe.model = Identity()
+    rec = {}
+    picks = [1, 6, 8, 9]
+    for tag, case in zip("abcd", (O.CASES[i] for i in picks)):
+        fs, ys, ft, R = (t.double() for t in O.inputs(case))
+        fs.requires_grad_(True)
+        ys.requires_grad_(True)
+        pred = pe.nfr(fs, ys, ft, reg=case[4])
+        assert pred.dtype == torch.float64
+        g_fs, g_ys = torch.autograd.grad(pred, (fs, ys), R)
+        rec.update({tag + "_feat_syn": fs.detach(), tag + "_y_syn": ys.detach(), tag + "_feat_tar": ft, tag + "_g_pred": R,
+                    tag + "_reg": np.float64(case[4]), tag + "_pred": pred.detach(), tag + "_g_feat_syn": g_fs, tag + "_g_y_syn": g_ys})
+    rec["cases"] = np.array(picks, dtype=np.int64)
+    os.makedirs(os.path.join(OUT, "nfr"), exist_ok=True)
+    npz(os.path.join("nfr", "values.npz"), **rec)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -854,7 +911,7 @@ def main():
                      ("g6", lambda: g6(networks, utils)), ("g7", lambda: g7(networks, utils)),
                      ("g9", lambda: g9(networks, utils)), ("g10", lambda: g10(networks, utils)),
                      ("g11", lambda: g11(networks, utils)), ("g12", lambda: g12(networks)), ("g13", lambda: g13(networks, utils)), ("g14", lambda: g14(networks, utils)), ("g15", g15), ("g17", g17),
-                     ("g16", lambda: g16(networks, utils))):
+                     ("g16", lambda: g16(networks, utils)), ("g18", g18)):
         if not only or name in only:
             fn()
 

@@ -20,11 +20,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvd_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernels.hip", "program.hip", "planner.cpp", "comm.cpp",
                                                          "coreset.hip", "clips_sample.hip", "eval_stats.hip", "still.hip", "still_rows.hip",
-                                                         "keyframes.hip", "traj.hip")]
+                                                         "nfr.hip", "keyframes.hip", "traj.hip")]
 CSRC_HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("frame_norm.h", "split16.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
 HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
 KEYFRAME_HEADER = os.path.join(_HERE, "..", "include", "vd_keyframes.h")      # the vdk_* entry points (csrc/keyframes.hip): under both hashes too
+NFR_HEADER = os.path.join(_HERE, "..", "include", "vd_nfr.h")      # the vdn_* entry points (csrc/nfr.hip): under both hashes as well
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
@@ -122,7 +123,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER, KEYFRAME_HEADER, *CSRC_HEADERS)
+        key = _file_hash(src, HEADER, KEYFRAME_HEADER, NFR_HEADER, *CSRC_HEADERS)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -172,7 +173,7 @@ def sources_hash() -> str:
     with, so that a figure measured on other kernels is refused instead of quoted."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER, KEYFRAME_HEADER] + CSRC_HEADERS:
+    for path in sorted(SOURCES) + [HEADER, KEYFRAME_HEADER, NFR_HEADER] + CSRC_HEADERS:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -182,6 +183,7 @@ _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_in
 _RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None, "const char*": ctypes.c_char_p}
 NAME_PATTERN = r"vd(?:t|s|sr)?_[a-z0-9_]+"          # include/vd_hip.h: vd_* and its three historical prefixes
 KEYFRAME_NAME_PATTERN = r"vdk_[a-z0-9_]+"          # include/vd_keyframes.h
+NFR_NAME_PATTERN = r"vdn_[a-z0-9_]+"          # include/vd_nfr.h
 _PROTOTYPE = r"(int64_t|int|void|const char\s*\*)\s*(%s)\s*\(([^()]*)\)"
 _PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+")
 
@@ -225,6 +227,13 @@ def keyframe_signatures() -> dict:
         return parse_header(f.read(), "include/vd_keyframes.h", KEYFRAME_NAME_PATTERN)
 
 
+@functools.lru_cache(maxsize=None)
+def nfr_signatures() -> dict:
+    """{name: (restype, [argtypes])} of include/vd_nfr.h (the ``vdn_*`` entry points), read and parsed once."""
+    with open(NFR_HEADER) as f:
+        return parse_header(f.read(), "include/vd_nfr.h", NFR_NAME_PATTERN)
+
+
 def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
     if name == "EXPORTS":
         return tuple(signatures())
@@ -239,10 +248,10 @@ class _Library(ctypes.CDLL):
 
 
 def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
-    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h and
-    include/vd_keyframes.h."""
+    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h,
+    include/vd_keyframes.h and include/vd_nfr.h."""
     L = _Library(path)
-    for name, (restype, argtypes) in list(signatures().items()) + list(keyframe_signatures().items()):
+    for name, (restype, argtypes) in list(signatures().items()) + list(keyframe_signatures().items()) + list(nfr_signatures().items()):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -577,6 +586,68 @@ def keyframe_reduce(g_clips: torch.Tensor, table) -> torch.Tensor:
     with torch.cuda.device(g_clips.device):
         run("vdk_keyframe_reduce", ptr(g_clips), n, ctypes.addressof(tab), H, W, ptr(out), stream_ptr(g_clips.device))
     return out
+
+
+VDN_MAX_SYN = 1024          # include/vd_nfr.h
+VDN_LDS_SYN = 128
+
+
+def _nfr_dims(feat_syn: torch.Tensor, feat_tar: torch.Tensor, labels: torch.Tensor, label_rows: str, what: str):
+    """Shapes, then dtypes and devices of one kernel-ridge call -> (n, m, d, c); ``labels`` is (n, c) or (m, c) (``label_rows``).
+    ``ValueError`` for shapes that do not fit or dimensions the op refuses, ``RuntimeError`` for what is not a contiguous fp32
+    tensor on a HIP device."""
+    label_name = "y_syn" if label_rows == "n" else "g_pred"
+    if feat_syn.dim() != 2 or feat_tar.dim() != 2 or labels.dim() != 2 or feat_tar.shape[1] != feat_syn.shape[1] \
+            or labels.shape[0] != (feat_syn.shape[0] if label_rows == "n" else feat_tar.shape[0]):
+        raise ValueError("%s: feat_syn (n, d), feat_tar (m, d) and %s (%s, c), not %s, %s and %s"
+                         % (what, label_name, label_rows, tuple(feat_syn.shape), tuple(feat_tar.shape), tuple(labels.shape)))
+    n, d, m, c = int(feat_syn.shape[0]), int(feat_syn.shape[1]), int(feat_tar.shape[0]), int(labels.shape[1])
+    if not (1 <= n <= VDN_MAX_SYN and m >= 1 and d >= 1 and c >= 1):
+        raise ValueError("%s: n %d (1..%d), m %d, d %d, c %d" % (what, n, VDN_MAX_SYN, m, d, c))
+    for name, t in (("feat_syn", feat_syn), ("feat_tar", feat_tar), (label_name, labels)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("%s: %s has no CPU path: a contiguous fp32 tensor on a HIP device" % (what, name))
+        if t.device != feat_syn.device:
+            raise ValueError("%s: the tensors live on one device" % what)
+    return n, m, d, c
+
+
+def nfr_forward(feat_syn: torch.Tensor, y_syn: torch.Tensor, feat_tar: torch.Tensor, reg: float = 1e-6):
+    """``vdn_nfr_forward`` on the current stream: the kernel ridge predictor of include/vd_nfr.h.  ``feat_syn`` (n, d), ``y_syn``
+    (n, c), ``feat_tar`` (m, d): contiguous fp32 on one HIP device.  -> (pred (m, c) fp64, workspace): the workspace, allocated
+    here, is what ``nfr_backward`` and ``nfr_status`` take.  Nothing synchronises with the host."""
+    n, m, d, c = _nfr_dims(feat_syn, feat_tar, y_syn, "n", "nfr_forward")
+    dev = feat_syn.device
+    nbytes = int(lib().vdn_nfr_workspace_bytes(n, m, d, c))
+    if nbytes < 0:
+        raise ValueError("nfr_forward: dimensions (%d, %d, %d, %d) are refused" % (n, m, d, c))
+    workspace = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    pred = torch.empty((m, c), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        run("vdn_nfr_forward", ptr(feat_syn), ptr(y_syn), ptr(feat_tar), n, m, d, c, float(reg), ptr(workspace), ptr(pred), stream_ptr(dev))
+    return pred, workspace
+
+
+def nfr_backward(feat_syn: torch.Tensor, feat_tar: torch.Tensor, g_pred: torch.Tensor, workspace: torch.Tensor, reg: float = 1e-6):
+    """``vdn_nfr_backward`` on the current stream, from the workspace of the ``nfr_forward`` call with the same features and
+    ``reg``: ``g_pred`` (m, c) contiguous fp32 -> (g_feat_syn (n, d), g_y_syn (n, c)), both fp64.  The workspace is only read."""
+    n, m, d, c = _nfr_dims(feat_syn, feat_tar, g_pred, "m", "nfr_backward")
+    dev = feat_syn.device
+    if not (workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.float64 and workspace.is_contiguous()
+            and workspace.numel() * 8 == int(lib().vdn_nfr_workspace_bytes(n, m, d, c))):
+        raise ValueError("nfr_backward: the workspace is not that of a forward call with these dimensions on %s" % dev)
+    g_feat = torch.empty((n, d), dtype=torch.float64, device=dev)
+    g_y = torch.empty((n, c), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        run("vdn_nfr_backward", ptr(feat_syn), ptr(feat_tar), ptr(g_pred), n, m, d, c, float(reg), ptr(workspace), ptr(g_feat), ptr(g_y),
+            stream_ptr(dev))
+    return g_feat, g_y
+
+
+def nfr_status(workspace: torch.Tensor) -> int:
+    """The status word of a workspace (a host read: it waits for the forward call): 0, or k + 1 when pivot k was the first that
+    was not positive and finite."""
+    return int(workspace[:1].view(torch.int64).item())
 
 
 class Comm:
