@@ -20,12 +20,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvd_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernels.hip", "program.hip", "planner.cpp", "comm.cpp",
                                                          "coreset.hip", "clips_sample.hip", "eval_stats.hip", "still.hip", "still_rows.hip",
-                                                         "nfr.hip", "keyframes.hip", "traj.hip")]
+                                                         "nfr.hip", "frepo.hip", "keyframes.hip", "traj.hip")]
 CSRC_HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("frame_norm.h", "split16.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
 HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
 KEYFRAME_HEADER = os.path.join(_HERE, "..", "include", "vd_keyframes.h")      # the vdk_* entry points (csrc/keyframes.hip): under both hashes too
 NFR_HEADER = os.path.join(_HERE, "..", "include", "vd_nfr.h")      # the vdn_* entry points (csrc/nfr.hip): under both hashes as well
+FREPO_HEADER = os.path.join(_HERE, "..", "include", "vd_frepo.h")      # the vdf_* entry points (csrc/frepo.hip): likewise
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
@@ -123,7 +124,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER, KEYFRAME_HEADER, NFR_HEADER, *CSRC_HEADERS)
+        key = _file_hash(src, HEADER, KEYFRAME_HEADER, NFR_HEADER, FREPO_HEADER, *CSRC_HEADERS)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -173,7 +174,7 @@ def sources_hash() -> str:
     with, so that a figure measured on other kernels is refused instead of quoted."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER, KEYFRAME_HEADER, NFR_HEADER] + CSRC_HEADERS:
+    for path in sorted(SOURCES) + [HEADER, KEYFRAME_HEADER, NFR_HEADER, FREPO_HEADER] + CSRC_HEADERS:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -184,6 +185,7 @@ _RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None, "const
 NAME_PATTERN = r"vd(?:t|s|sr)?_[a-z0-9_]+"          # include/vd_hip.h: vd_* and its three historical prefixes
 KEYFRAME_NAME_PATTERN = r"vdk_[a-z0-9_]+"          # include/vd_keyframes.h
 NFR_NAME_PATTERN = r"vdn_[a-z0-9_]+"          # include/vd_nfr.h
+FREPO_NAME_PATTERN = r"vdf_[a-z0-9_]+"          # include/vd_frepo.h
 _PROTOTYPE = r"(int64_t|int|void|const char\s*\*)\s*(%s)\s*\(([^()]*)\)"
 _PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+")
 
@@ -234,6 +236,13 @@ def nfr_signatures() -> dict:
         return parse_header(f.read(), "include/vd_nfr.h", NFR_NAME_PATTERN)
 
 
+@functools.lru_cache(maxsize=None)
+def frepo_signatures() -> dict:
+    """{name: (restype, [argtypes])} of include/vd_frepo.h (the ``vdf_*`` entry points), read and parsed once."""
+    with open(FREPO_HEADER) as f:
+        return parse_header(f.read(), "include/vd_frepo.h", FREPO_NAME_PATTERN)
+
+
 def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
     if name == "EXPORTS":
         return tuple(signatures())
@@ -249,9 +258,10 @@ class _Library(ctypes.CDLL):
 
 def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
     """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h,
-    include/vd_keyframes.h and include/vd_nfr.h."""
+    include/vd_keyframes.h, include/vd_nfr.h and include/vd_frepo.h."""
     L = _Library(path)
-    for name, (restype, argtypes) in list(signatures().items()) + list(keyframe_signatures().items()) + list(nfr_signatures().items()):
+    for name, (restype, argtypes) in list(signatures().items()) + list(keyframe_signatures().items()) + list(nfr_signatures().items()) \
+            + list(frepo_signatures().items()):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -648,6 +658,75 @@ def nfr_status(workspace: torch.Tensor) -> int:
     """The status word of a workspace (a host read: it waits for the forward call): 0, or k + 1 when pivot k was the first that
     was not positive and finite."""
     return int(workspace[:1].view(torch.int64).item())
+
+
+VDF_ADAM_MAX = 16          # include/vd_frepo.h
+
+
+class VdfAdamSeg(ctypes.Structure):
+    _fields_ = [("p", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("g", ctypes.c_void_p), ("n", ctypes.c_int64),
+                ("step_size", ctypes.c_float), ("lr_wd", ctypes.c_float), ("first_block", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class VdfAdamBatch(ctypes.Structure):
+    _fields_ = [("nseg", ctypes.c_int32), ("reserved", ctypes.c_int32), ("beta1", ctypes.c_float), ("one_minus_beta1", ctypes.c_float),
+                ("beta2", ctypes.c_float), ("one_minus_beta2", ctypes.c_float), ("bc2_sqrt", ctypes.c_float), ("eps", ctypes.c_float),
+                ("seg", VdfAdamSeg * VDF_ADAM_MAX)]
+
+
+def mse_loss(logits: torch.Tensor, targets: torch.Tensor):
+    """``vdf_mse_loss`` on the current stream: ``nn.MSELoss()`` of ``logits`` (B, K) against ``targets`` (B, K), both contiguous
+    fp32 on one HIP device -> (loss: a fresh device scalar, dlogits (B, K))."""
+    if logits.dim() != 2 or tuple(targets.shape) != tuple(logits.shape) or logits.numel() == 0:
+        raise ValueError("mse_loss: logits (B, K) and targets (B, K), not %s and %s" % (tuple(logits.shape), tuple(targets.shape)))
+    for name, t in (("logits", logits), ("targets", targets)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == logits.device):
+            raise RuntimeError("mse_loss: %s has no CPU path: a contiguous fp32 tensor on one HIP device" % name)
+    B, K = int(logits.shape[0]), int(logits.shape[1])
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    dlog = torch.empty((B, K), dtype=torch.float32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        run("vdf_mse_loss", ptr(logits), ptr(targets), B, K, ptr(loss), ptr(dlog), stream_ptr(logits.device))
+    return loss, dlog
+
+
+def adam_constants(lr: float, beta1: float, beta2: float, step: int):
+    """(step_size, bc2_sqrt) of step ``step`` >= 1 in double, exactly as ``torch.optim.Adam`` computes them
+    (``lr / (1 - beta1 ** step)``, ``(1 - beta2 ** step) ** 0.5``); the launch rounds each to float once."""
+    return float(lr) / (1.0 - float(beta1) ** int(step)), (1.0 - float(beta2) ** int(step)) ** 0.5
+
+
+def adam_multi(segments, beta1: float, beta2: float, eps: float, step: int) -> None:
+    """``vdf_adam_multi`` on the current stream: one Adam / AdamW step ``step`` (>= 1, shared) over ``segments``, a sequence of
+    ``(p, m, v, g, lr, weight_decay)`` -- four fp32 device tensors of one element count, contiguous (views at any float offset
+    are fine), updated in place but for ``g``; ``weight_decay`` is AdamW's decoupled decay (0: Adam).  One launch per
+    ``VDF_ADAM_MAX`` segments."""
+    segments = list(segments)
+    if int(step) < 1:
+        raise ValueError("adam_multi: step %r (the count after the increment, >= 1)" % (step,))
+    if not segments:
+        return
+    dev = segments[0][0].device
+    for p, m, v, g, _, _ in segments:
+        for name, t in (("p", p), ("m", m), ("v", v), ("g", g)):
+            if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
+                raise RuntimeError("adam_multi: %s has no CPU path: contiguous fp32 tensors on one HIP device" % name)
+            if t.numel() != p.numel() or t.numel() < 1:
+                raise ValueError("adam_multi: p, m, v and g hold %s elements" % ([x.numel() for x in (p, m, v, g)],))
+    st = stream_ptr(dev)
+    with torch.cuda.device(dev):
+        for lo in range(0, len(segments), VDF_ADAM_MAX):
+            part = segments[lo:lo + VDF_ADAM_MAX]
+            b = VdfAdamBatch()
+            b.nseg = len(part)
+            b.beta1, b.one_minus_beta1, b.beta2, b.one_minus_beta2 = beta1, 1.0 - beta1, beta2, 1.0 - beta2
+            b.eps = eps
+            b.bc2_sqrt = adam_constants(0.0, beta1, beta2, step)[1]
+            for k, (p, m, v, g, lr, wd) in enumerate(part):
+                s = b.seg[k]
+                s.p, s.m, s.v, s.g, s.n = ptr(p), ptr(m), ptr(v), ptr(g), p.numel()
+                s.step_size, s.lr_wd = adam_constants(lr, beta1, beta2, step)[0], float(lr) * float(wd)
+            run("vdf_adam_multi", ctypes.addressof(b), st)
 
 
 class Comm:

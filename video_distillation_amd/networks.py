@@ -14,6 +14,9 @@ Execution
   * ``hip_train_step`` -- one ``epoch('train')`` iteration of ``evaluate_synset`` (forward, CE
     loss, all parameter gradients, SGD with momentum / weight decay) on the HIP path
     (train.TrainEngine: weight gradients are tile programs of the same MFMA kernel).
+  * ``hip_regress_step`` -- the same step for FRePo's networks: MSE on soft labels (``vdf_mse_loss``) and Adam / AdamW over
+    the eight tensors in one launch (``vdf_adam_multi``); ``embed_exact`` -- no-gradient features in hi+lo pairs with the exact
+    weights, the target side of ``nfr.nfr(exact=True)``.
   * ``net(x)`` / ``embed(x)`` with parameters that require a gradient are autograd Functions over the same HIP
     passes, differentiable TWICE: ``torch.autograd.grad(criterion(net(x), y), params, create_graph=True)`` -- the
     reference's DC / MTT call (distill_baseline.py:250) -- and a ``backward()`` through a loss on those gradients run
@@ -532,6 +535,64 @@ class ConvNet3D(nn.Module):
             optimizer.state[p]["momentum_buffer"] = b
             torch.autograd.graph.increment_version(p)
         return logits, loss
+
+    # -- regression step on the HIP path (FRePo: MSE on soft labels, Adam / AdamW) ---------------------
+    @staticmethod
+    def _adam_group_ok(optimizer, g) -> bool:
+        """One param group of a torch Adam / AdamW that ``vdf_adam_multi`` restates: no amsgrad / maximize / capturable / fused /
+        differentiable, a host-number learning rate, and weight decay only in its decoupled (AdamW) form."""
+        if g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("fused") or g.get("differentiable"):
+            return False
+        if isinstance(g["lr"], torch.Tensor):
+            return False
+        decoupled = isinstance(optimizer, torch.optim.AdamW) or bool(g.get("decoupled_weight_decay"))
+        return decoupled or g.get("weight_decay", 0) == 0
+
+    def hip_regress_trainable(self, x, optimizer, criterion) -> bool:
+        """True when (net, optimiser, loss) is the combination FRePo trains its networks with (distill_s2d.py:284, 293;
+        lib_torch/utils.py:565, 571): ``torch.optim.Adam`` / ``AdamW`` (no amsgrad, maximize or capturable) in one param group
+        over exactly this module's parameters, all contiguous fp32 on the device, and ``nn.MSELoss`` with mean reduction."""
+        if not (self._hip_ok and x.is_cuda and x.dim() == 5 and x.shape[2] == 3):
+            return False
+        if type(optimizer) not in (torch.optim.Adam, torch.optim.AdamW) or len(optimizer.param_groups) != 1:
+            return False
+        g = optimizer.param_groups[0]
+        if not self._adam_group_ok(optimizer, g):
+            return False
+        mine = list(self.parameters())
+        if len(g["params"]) != len(mine) or any(a is not b for a, b in zip(g["params"], mine)):
+            return False
+        if any((not p.is_cuda) or p.dtype != torch.float32 or not p.is_contiguous() for p in mine):
+            return False
+        return type(criterion) is nn.MSELoss and criterion.reduction == "mean"
+
+    def hip_regress_step(self, x, y, optimizer):
+        """forward + ``nn.MSELoss()`` on the soft labels ``y`` (B, K) + backward + ``optimizer.step()`` (Adam / AdamW) for one
+        batch, on the HIP path: ``hip_train_step`` with ``vdf_mse_loss`` for the loss and ONE ``vdf_adam_multi`` launch for the
+        eight tensors.  The optimiser's state lives where torch keeps it (``step``, ``exp_avg``, ``exp_avg_sq``: torch's keys,
+        dtypes and shapes), the learning rate is read from the param group at the call.  Returns (logits, loss)."""
+        from . import frepo
+        te = self._train_engine(x)
+        params = list(self.parameters())
+        te.side_wgrad = True
+        try:
+            loss, logits, grads = te.regress_and_grads(x, y, params, self._dropout_mask(x, te))
+        finally:
+            te.side_wgrad = False
+        frepo.adam_update(optimizer, optimizer.param_groups[0], params, grads)
+        return logits, loss
+
+    def embed_exact(self, x):
+        """Features of clips that carry no gradient in the ``syn`` precision (hi+lo pairs) with the exact weights: no dithered
+        operand sets, no rounding of the weights, and the memory of the latest dithered batch (``real_dither`` "auto") stays as
+        it is.  The target side of ``nfr.nfr(exact=True)``: a kernel ridge solve tells two close synthetic clips apart only if
+        both sides see the same weights."""
+        self._check_hip(x, "embed_exact")
+        x = x.detach()
+        eng = get_engine(P.NetGeometry(x.shape[1], x.shape[3], x.shape[4]), _PRECISION["syn"], x.device, _PRECISION["bwd"])
+        self._sync_engine(eng)
+        with torch.no_grad():
+            return eng.forward(x)
 
     def forward(self, x):
         """networks.py:738-745 on the HIP path.  Evaluation without gradient: MFMA features + fused head kernel.

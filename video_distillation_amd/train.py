@@ -192,8 +192,8 @@ class TrainEngine:
         logit-gradient buffers.  -> (x, labels [as the kernels read them], nb, arg-max bytes, head state, loss_c, dlog)."""
         eng, B = self.eng, int(x.shape[0])
         x = x.detach().to(torch.float32).contiguous()
-        labels = labels.to(self.device, torch.int64).contiguous()
-        with engine.batched_packs():          # (forward + input-gradient operands of the three levels: one launch)
+        labels = None if labels is None else labels.to(self.device, torch.int64).contiguous()      # (None: regress_and_grads)
+        with engine.batched_packs():         # (forward + input-gradient operands of the three levels: one launch)
             eng.set_weights(params[:6])
             for li in (1, 2):
                 for dp in eng.bwd[li]:
@@ -221,6 +221,29 @@ class TrainEngine:
             state.update(nb=nb, am=am, dropped=hs["dropped"], logits=logits, dlog=dlog, amt=hs["amt"], mask=hs["mask"],
                          wl=hs["wl"], act_plane=act_plane, x=x)
         return loss_c.mean(), logits, g
+
+    def regress_and_grads(self, x: torch.Tensor, targets: torch.Tensor, params: Sequence[torch.Tensor],
+                          mask: Optional[torch.Tensor] = None):
+        """``loss_and_grads`` with ``nn.MSELoss()`` on float targets (B, K) in the place of the cross-entropy (FRePo's networks:
+        distill_s2d.py:145-156): the same forward, head and backward passes, ``vdf_mse_loss`` where ``vd_ce_loss`` stands.
+        Returns (MSE loss [device scalar], logits (B,K), [8 gradient tensors])."""
+        x, _, nb, am, hs, _, _ = self._forward_head(x, None, params, mask)
+        logits = hs["logits"]
+        if tuple(targets.shape) != tuple(logits.shape):
+            raise ValueError("regress_and_grads: targets %s for logits %s" % (tuple(targets.shape), tuple(logits.shape)))
+        loss, dlog = hip.mse_loss(logits, targets.detach().to(self.device, torch.float32).contiguous())
+        self.gflat.zero_()
+        g = self.grads()
+        g_feat = self.head_backward(hs, dlog, g[6], g[7])
+        self.feat_backward(x, nb, am, g_feat, g)
+        return loss, logits, g
+
+    def adam_step(self, params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avg: Sequence[torch.Tensor],
+                  exp_avg_sq: Sequence[torch.Tensor], lr: float, betas: Tuple[float, float], eps: float, weight_decay: float,
+                  step: int) -> None:
+        """In-place torch.optim.Adam / AdamW (decoupled ``weight_decay``) update number ``step`` of all tensors: one launch."""
+        hip.adam_multi([(p, m, v, g, lr, weight_decay) for p, m, v, g in zip(params, exp_avg, exp_avg_sq, grads)],
+                       betas[0], betas[1], eps, step)
 
     def loss_and_grads_grouped(self, x: torch.Tensor, labels: torch.Tensor, params: Sequence[torch.Tensor], groups: int,
                                mask: Optional[torch.Tensor] = None):
