@@ -238,6 +238,8 @@ def test_clip_sizes_off_the_multiple_of_four(dims):
       4 x 65 x 63: level-0 input gradient as four parity-class programs with pixel output, one-type frame-tile forward at width 63;
       4 x 70 x 58: four-type level-0 forward without frame tiles, (MW, MTW) = (1, 2) level-1 forward, level-2 parity classes of
                    32 / 64 / 32 / 64 clips per box.
+    (tests/test_gpu_forward_level.py runs the forward programs of these sizes on the device, and 4 x 104 x 112 for the 7-tile level-1
+    families; tests/test_forward_level_cpu.py asserts what each of its sizes plans to.)
     Level-0 / level-1 forward and every input-gradient program against fp64 conv3d / autograd; the input gradients of levels 1
     and 2 with ncl + 1 clips (largest ncl of the level's programs), so that every program's last clip group is ragged."""
     geo = P.NetGeometry(*dims)
