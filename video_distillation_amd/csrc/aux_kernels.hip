@@ -1159,7 +1159,14 @@ extern "C" int vd_hallucinator_bwd(const float* g_out, const float* stat, const 
     // 203 MB of algorithmic traffic in 0.3 ms
     static const int fused = getenv("VD_HAL_FUSED") ? atoi(getenv("VD_HAL_FUSED")) : 1;
     const int tiles_x = (W + HAL_TW - 1) / HAL_TW, tiles_y = (H + HAL_TH - 1) / HAL_TH;
-    if (fused && (g_w != nullptr) == (g_b != nullptr) && (fused >= 2 || (int64_t)n * tiles_x * tiles_y >= 1024)) {
+    // Ordered mode (vd_set_deterministic / VD_DETERMINISTIC): both forms close with one fp32 atomic per workgroup onto the
+    // same <= 327 parameter-gradient addresses, in whatever order the workgroups finish.  The ordered form is the two-kernel one with
+    // ONE workgroup per parameter job: its threads walk the pixel columns in a fixed order, the wave and workgroup sums have a fixed
+    // order, and each address takes a single add onto the caller's zero.  (g_dyn / g_stat take one add per element and clip: they
+    // are order-free wherever no two clips share a memory row, which is how utils.Conv3DNet calls this.)  Slow at full size -- one
+    // workgroup walks every column -- and meant for reproducing a run, not for timing one.
+    const bool ordered = vd_get_deterministic() != 0;
+    if (!ordered && fused && (g_w != nullptr) == (g_b != nullptr) && (fused >= 2 || (int64_t)n * tiles_x * tiles_y >= 1024)) {
         int64_t grid = (int64_t)n * tiles_x * tiles_y;
         if (grid > 512) grid = 512;
         hipLaunchKernelGGL(hal_bwd_fused_kernel, dim3((unsigned)grid), dim3(256), 0, st, g_out, stat, dyn, sidx, didx, w, n, T, H, W,
@@ -1175,6 +1182,7 @@ extern "C" int vd_hallucinator_bwd(const float* g_out, const float* stat, const 
         // (256 blocks per job: more blocks cost more in the closing atomics -- every block adds onto the same <= 81 addresses --
         //  than they gain in parallelism: 0.17 ms at 256, 0.25 at 1024, 0.43 at 2560 for 50 clips 112x112x16)
         if (chunks > 256) chunks = 256;
+        if (ordered) chunks = 1;
         hipLaunchKernelGGL(hal_bwd_param_kernel, dim3((unsigned)chunks, 6), dim3(256), 0, st, g_out, stat, dyn, sidx,
                            didx, n, T, H, W, g_w, g_b);
         e = (int)hipGetLastError();

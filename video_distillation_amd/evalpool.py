@@ -11,6 +11,11 @@ waiting.  The networks are independent of each other, and so are the three test 
   * exchange: one fp64 tensor (num_eval, 4, 8 + 2K) -- rows 0..2 the passes' ``vd_eval_stats`` records, row 3 the owner's last
     training epoch -- zero except where this rank wrote, summed by one all-reduce.  Every slot has one writer: the sum is exact.
 
+What a network trains on, how it is trained and how one pass is tested is a ``Recipe``.  The default one is the reference's
+cross-entropy evaluation as above (SGD, three passes, ``vd_eval_stats``); ``frepo.EVAL_RECIPE`` is FRePo's regression evaluation
+(AdamW on soft labels, ONE test pass through ``vdr_regress_stats``, whose record has the same slots): then there are
+``passes + 1`` rows per network and ``(1 + passes) * num_eval`` units.
+
 All global generators are seeded from (seed, i, 0) before network ``i`` is created and trained and from (seed, i, 1 + p) before
 pass ``p`` of its test, so what a unit computes depends neither on the rank that runs it nor on what that rank ran before.
 Every rank derives the same result from the reduced tensor.  A rank that raises inside a phase still takes part in the error
@@ -38,17 +43,19 @@ def train_rank(i: int, world: int) -> int:
     return i % world
 
 
-def unit_rank(i: int, p: int, num_eval: int, world: int) -> int:
-    """The rank that runs test pass ``p`` of network ``i``.  The units numbered ``i + p * num_eval`` are dealt round-robin: every
-    unit has one rank, loads differ by at most one unit, and all three passes stay with the owner when ``world`` divides
-    ``num_eval`` (and at ``world`` 1)."""
+def unit_rank(i: int, p: int, num_eval: int, world: int, passes: int = PASSES) -> int:
+    """The rank that runs test pass ``p`` (of ``passes``) of network ``i``.  The units numbered ``i + p * num_eval`` are dealt
+    round-robin: every unit has one rank, loads differ by at most one unit, and all passes stay with the owner when ``world``
+    divides ``num_eval`` (and at ``world`` 1)."""
+    if not 0 <= p < passes:
+        raise ValueError("unit_rank: pass %d of %d" % (p, passes))
     return (i + p * num_eval) % world
 
 
-def assignment(num_eval: int, world: int) -> Dict[str, list]:
+def assignment(num_eval: int, world: int, passes: int = PASSES) -> Dict[str, list]:
     """{"train": [rank of network i], "test": [[rank of pass p of network i]]}"""
     return {"train": [train_rank(i, world) for i in range(num_eval)],
-            "test": [[unit_rank(i, p, num_eval, world) for p in range(PASSES)] for i in range(num_eval)]}
+            "test": [[unit_rank(i, p, num_eval, world, passes) for p in range(passes)] for i in range(num_eval)]}
 
 
 def unit_seed(seed: int, i: int, k: int) -> int:
@@ -131,6 +138,32 @@ def test_pass(net: nn.Module, testloader, args, rec: torch.Tensor) -> torch.Tens
     return rec
 
 
+class Recipe:
+    """What ``evaluate_pool`` runs per network.
+
+      * ``data(i)``                             -> (images_train, labels_train) of network ``i``; called by its owner after the
+                                                   generators were seeded for the unit.  None: the arguments of ``evaluate_pool``
+      * ``train(net, x, y, args)``              -> (loss, accuracy) of the last training epoch
+      * ``test_pass(net, loader, args, rec)``   one iteration of the loader, accumulated into the record ``rec``
+      * ``passes``                              test passes per network
+
+    ``derive`` reads every record by the slots of ``vd_eval_stats``; ``loss_scale(K)`` divides slot 1 further (the regression
+    record sums over the K classes of a clip, the mean-squared error divides by them)."""
+
+    def __init__(self, train, test_pass, passes: int, data=None, loss_scale=None):
+        if int(passes) < 1:
+            raise ValueError("Recipe: at least one test pass")
+        self.train, self.test_pass, self.passes, self.data, self.loss_scale = train, test_pass, int(passes), data, loss_scale
+
+    def with_data(self, data) -> "Recipe":
+        return Recipe(self.train, self.test_pass, self.passes, data, self.loss_scale)
+
+
+def default_recipe(mode: str = 'none') -> Recipe:
+    """The reference's cross-entropy evaluation: ``train_network`` in ``mode``, three passes of ``test_pass``."""
+    return Recipe(lambda net, x, y, args: train_network(net, x, y, args, mode), test_pass, PASSES)
+
+
 def _live(world: int) -> bool:
     if world <= 1:
         return False
@@ -162,38 +195,42 @@ def _end_of_phase(name: str, error: Optional[BaseException], live: bool, xdev) -
         raise RuntimeError("evaluate_pool: another rank failed in the %s phase" % name)
 
 
-def derive(records: torch.Tensor, num_eval: int, world: int) -> dict:
-    """The result every rank computes from the reduced (num_eval, 4, 8 + 2K) tensor."""
+def derive(records: torch.Tensor, num_eval: int, world: int, passes: int = PASSES, loss_scale: float = 1.0) -> dict:
+    """The result every rank computes from the reduced (num_eval, passes + 1, 8 + 2K) tensor; ``loss_test`` is slot 1 over the
+    clips seen and over ``loss_scale``."""
+    if int(records.shape[1]) != passes + 1:
+        raise ValueError("derive: %d rows per network for %d passes" % (int(records.shape[1]), passes))
     R = records.detach().cpu().to(torch.float64)
     K = (R.shape[2] - hip.EVAL_STATS_HEAD) // 2
     H = hip.EVAL_STATS_HEAD
     out = {"num_eval": num_eval, "world": world, "num_classes": K, "acc_test": [], "loss_test": [], "top1": [], "top3": [], "top5": [],
            "acc_per_class": [], "acc_train": [], "loss_train": [], "test_clips": [], "labels_out_of_range": []}
     for i in range(num_eval):
-        tot = R[i, :PASSES].sum(0)              # (integers and three cross-entropy sums, added in pass order)
+        tot = R[i, :passes].sum(0)              # (integers and the passes' loss sums, added in pass order)
         n = float(tot[0])
         if n <= 0:
             raise RuntimeError("evaluate_pool: network %d saw no test clip with a label in [0, %d)" % (i, K))
         out["test_clips"].append(int(n))
         out["labels_out_of_range"].append(int(tot[5]))
-        out["loss_test"].append(float(tot[1]) / n)
+        out["loss_test"].append(float(tot[1]) / n / loss_scale if loss_scale != 1.0 else float(tot[1]) / n)
         out["acc_test"].append(float(tot[2]) / n)           # sum of top-1 hits / sum of clips over the three passes, as epoch()
         out["top1"].append(float(tot[2]) / n)
         out["top3"].append(float(tot[3]) / n)
         out["top5"].append(float(tot[4]) / n)
         hits, seen = tot[H:H + K].tolist(), tot[H + K:H + 2 * K].tolist()
         out["acc_per_class"].append([h / s if s > 0 else None for h, s in zip(hits, seen)])
-        out["loss_train"].append(float(R[i, TRAIN_ROW, 0]))
-        out["acc_train"].append(float(R[i, TRAIN_ROW, 1]))
+        out["loss_train"].append(float(R[i, passes, 0]))          # (the training row follows the passes: TRAIN_ROW at three)
+        out["acc_train"].append(float(R[i, passes, 1]))
     out["mean"] = float(np.mean(out["acc_test"]))
     out["std"] = float(np.std(out["acc_test"]))
-    out["assignment"] = assignment(num_eval, world)
+    out["assignment"] = assignment(num_eval, world, passes)
     out["records"] = R
     return out
 
 
 def evaluate_pool(make_net, images_train, labels_train, testloader, args, *, num_eval: int, seed: int, mode: str = 'none',
-                  rank: int = 0, world: int = 1, num_classes: Optional[int] = None, on_trained=None) -> dict:
+                  rank: int = 0, world: int = 1, num_classes: Optional[int] = None, on_trained=None,
+                  recipe: Optional[Recipe] = None) -> dict:
     """Train ``num_eval`` networks on the synthetic set and test each three times, dealt over ``world`` ranks (module
     docstring).  Every rank calls it with the same arguments and its own ``rank`` and gets the same dict: per network
     ``acc_test``, ``loss_test``, ``top1`` / ``top3`` / ``top5``, ``acc_per_class`` (None for a class never seen),
@@ -203,7 +240,9 @@ def evaluate_pool(make_net, images_train, labels_train, testloader, args, *, num
     ``make_net(i)`` builds network ``i`` after the generators were seeded (None: ConvNet3D for the geometry of
     ``images_train``, mode 'none').  It must not reseed from the clock as ``utils.get_network`` does.  ``args`` is
     ``evaluate_synset``'s namespace.  ``num_classes``: width of the records (default: from the training labels).
-    ``on_trained(i, net)`` is called by the owner of network ``i`` after its training."""
+    ``on_trained(i, net)`` is called by the owner of network ``i`` after its training.  ``recipe``: None is the reference's
+    cross-entropy evaluation (``default_recipe(mode)``); another ``Recipe`` trains and tests its own way with its own number of
+    passes, ``mode`` 'none' only."""
     if mode not in ('none', 'multi-static'):
         raise NotImplementedError
     if num_eval < 1 or not 0 <= rank < world:
@@ -214,10 +253,15 @@ def evaluate_pool(make_net, images_train, labels_train, testloader, args, *, num
         if mode != 'none':
             raise ValueError("evaluate_pool: pass make_net for mode %r" % mode)
         make_net = convnet3d_factory(num_classes, images_train.shape[3:5], int(images_train.shape[1]))
+    if recipe is None:
+        recipe = default_recipe(mode)
+    elif mode != 'none':
+        raise ValueError("evaluate_pool: a recipe of its own runs in mode 'none'")
+    PASSES, TRAIN_ROW = recipe.passes, recipe.passes          # (rows per network: the passes, then the owner's training epoch)
     K = int(num_classes)
     live = _live(world)
     xdev = _exchange_device(args.device, live)
-    plan = assignment(num_eval, world)
+    plan = assignment(num_eval, world, PASSES)
     records = torch.zeros((num_eval, PASSES + 1, hip.EVAL_STATS_HEAD + 2 * K), dtype=torch.float64, device=xdev)
     times = torch.zeros(num_eval * (PASSES + 1) + world * 3, dtype=torch.float64, device=xdev)
     net_times = times[:num_eval * (PASSES + 1)].view(num_eval, PASSES + 1)      # [i][p] test pass p, [i][3] training
@@ -241,7 +285,8 @@ def evaluate_pool(make_net, images_train, labels_train, testloader, args, *, num
             net = make_net(i).to(args.device)
             if mine:
                 t0 = time.time()
-                loss_train, acc_train = train_network(net, images_train, labels_train, args, mode)
+                x_train, y_train = (images_train, labels_train) if recipe.data is None else recipe.data(i)
+                loss_train, acc_train = recipe.train(net, x_train, y_train, args)
                 sync()
                 net_times[i, TRAIN_ROW] = time.time() - t0
                 records[i, TRAIN_ROW, 0] = loss_train
@@ -283,7 +328,7 @@ def evaluate_pool(make_net, images_train, labels_train, testloader, args, *, num
                     continue
                 seed_all(unit_seed(seed, i, 1 + p))
                 t0 = time.time()
-                rec = test_pass(nets[i], testloader, args, hip.eval_stats_record(K, args.device))
+                rec = recipe.test_pass(nets[i], testloader, args, hip.eval_stats_record(K, args.device))
                 sync()
                 records[i, p].copy_(rec)
                 net_times[i, p] = time.time() - t0
@@ -296,7 +341,7 @@ def evaluate_pool(make_net, images_train, labels_train, testloader, args, *, num
     if live:
         distill._all_reduce(records)
         distill._all_reduce(times)
-    out = derive(records, num_eval, world)
+    out = derive(records, num_eval, world, PASSES, 1.0 if recipe.loss_scale is None else float(recipe.loss_scale(K)))
     tn, tr = net_times.cpu(), rank_times.cpu()
     out["times"] = {"train_s": tn[:, TRAIN_ROW].tolist(), "test_pass_s": tn[:, :PASSES].tolist(),
                     "rank_train_s": tr[:, 0].tolist(), "rank_move_s": tr[:, 1].tolist(), "rank_test_s": tr[:, 2].tolist()}

@@ -19,7 +19,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvd_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernels.hip", "program.hip", "planner.cpp", "comm.cpp",
-                                                         "coreset.hip", "clips_sample.hip", "eval_stats.hip", "still.hip", "still_rows.hip",
+                                                         "coreset.hip", "clips_sample.hip", "eval_stats.hip", "regress_stats.hip", "still.hip", "still_rows.hip",
                                                          "nfr.hip", "frepo.hip", "keyframes.hip", "traj.hip")]
 CSRC_HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("frame_norm.h", "split16.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
@@ -27,6 +27,7 @@ HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
 KEYFRAME_HEADER = os.path.join(_HERE, "..", "include", "vd_keyframes.h")      # the vdk_* entry points (csrc/keyframes.hip): under both hashes too
 NFR_HEADER = os.path.join(_HERE, "..", "include", "vd_nfr.h")      # the vdn_* entry points (csrc/nfr.hip): under both hashes as well
 FREPO_HEADER = os.path.join(_HERE, "..", "include", "vd_frepo.h")      # the vdf_* entry points (csrc/frepo.hip): likewise
+REGRESS_HEADER = os.path.join(_HERE, "..", "include", "vd_regress.h")      # the vdr_* entry point (csrc/regress_stats.hip): likewise
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
@@ -124,7 +125,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER, KEYFRAME_HEADER, NFR_HEADER, FREPO_HEADER, *CSRC_HEADERS)
+        key = _file_hash(src, HEADER, KEYFRAME_HEADER, NFR_HEADER, FREPO_HEADER, REGRESS_HEADER, *CSRC_HEADERS)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -174,7 +175,7 @@ def sources_hash() -> str:
     with, so that a figure measured on other kernels is refused instead of quoted."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER, KEYFRAME_HEADER, NFR_HEADER, FREPO_HEADER] + CSRC_HEADERS:
+    for path in sorted(SOURCES) + [HEADER, KEYFRAME_HEADER, NFR_HEADER, FREPO_HEADER, REGRESS_HEADER] + CSRC_HEADERS:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -186,6 +187,7 @@ NAME_PATTERN = r"vd(?:t|s|sr)?_[a-z0-9_]+"          # include/vd_hip.h: vd_* and
 KEYFRAME_NAME_PATTERN = r"vdk_[a-z0-9_]+"          # include/vd_keyframes.h
 NFR_NAME_PATTERN = r"vdn_[a-z0-9_]+"          # include/vd_nfr.h
 FREPO_NAME_PATTERN = r"vdf_[a-z0-9_]+"          # include/vd_frepo.h
+REGRESS_NAME_PATTERN = r"vdr_[a-z0-9_]+"          # include/vd_regress.h
 _PROTOTYPE = r"(int64_t|int|void|const char\s*\*)\s*(%s)\s*\(([^()]*)\)"
 _PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+")
 
@@ -243,6 +245,13 @@ def frepo_signatures() -> dict:
         return parse_header(f.read(), "include/vd_frepo.h", FREPO_NAME_PATTERN)
 
 
+@functools.lru_cache(maxsize=None)
+def regress_signatures() -> dict:
+    """{name: (restype, [argtypes])} of include/vd_regress.h (the ``vdr_*`` entry point), read and parsed once."""
+    with open(REGRESS_HEADER) as f:
+        return parse_header(f.read(), "include/vd_regress.h", REGRESS_NAME_PATTERN)
+
+
 def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
     if name == "EXPORTS":
         return tuple(signatures())
@@ -258,10 +267,10 @@ class _Library(ctypes.CDLL):
 
 def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
     """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h,
-    include/vd_keyframes.h, include/vd_nfr.h and include/vd_frepo.h."""
+    include/vd_keyframes.h, include/vd_nfr.h, include/vd_frepo.h and include/vd_regress.h."""
     L = _Library(path)
     for name, (restype, argtypes) in list(signatures().items()) + list(keyframe_signatures().items()) + list(nfr_signatures().items()) \
-            + list(frepo_signatures().items()):
+            + list(frepo_signatures().items()) + list(regress_signatures().items()):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -382,6 +391,46 @@ def eval_stats(logits: torch.Tensor, labels: torch.Tensor, rec: torch.Tensor) ->
     ce = (m + torch.log(torch.exp(z - m).sum(1, keepdim=True)) - zy)[:, 0]
     rec[0] += float(y.numel())
     rec[1] += ce.sum()
+    for slot, k in ((2, 1), (3, 3), (4, 5)):
+        rec[slot] += float((rank < k).sum())
+    rec[EVAL_STATS_HEAD:EVAL_STATS_HEAD + K] += torch.bincount(y[rank < 1], minlength=K).double()
+    rec[EVAL_STATS_HEAD + K:] += torch.bincount(y, minlength=K).double()
+    return rec
+
+
+def regress_stats(logits: torch.Tensor, labels: torch.Tensor, rec: torch.Tensor) -> torch.Tensor:
+    """Accumulate the regression test statistics of one batch -- clips, the sum of squared errors against ``frepo.soft_labels``
+    (``one_hot - 1 / K`` in fp32), top-1/3/5 hits, labels out of range, hits and clips per class -- into ``rec``, a record of
+    ``eval_stats_record`` (vdr_regress_stats, one launch on the current stream; layout: include/vd_regress.h).  ``labels`` are
+    the integer labels.  Device tensors always go to the kernel; CPU tensors take the same definitions in torch fp64, as
+    ``eval_stats`` does, so that the host logic of evalpool.py runs under gloo without a GPU."""
+    if logits.dim() != 2:
+        raise ValueError("regress_stats: logits (B, K)")
+    B, K = int(logits.shape[0]), int(logits.shape[1])
+    if K < 1 or tuple(labels.shape) != (B,) or labels.is_floating_point() or rec.dtype != torch.float64 \
+            or rec.numel() != EVAL_STATS_HEAD + 2 * K or not rec.is_contiguous():
+        raise ValueError("regress_stats: logits (B, K), integer labels (B,), rec %d contiguous doubles" % (EVAL_STATS_HEAD + 2 * K))
+    if logits.device != labels.device or logits.device != rec.device:
+        raise ValueError("regress_stats: logits, labels and rec live on one device")
+    z = logits.detach().to(torch.float32).contiguous()
+    y = labels.detach().to(torch.int64).contiguous()
+    if z.is_cuda:
+        with torch.cuda.device(z.device):
+            run("vdr_regress_stats", ptr(z), ptr(y), B, K, ptr(rec), stream_ptr(z.device))
+        return rec
+    if B == 0:
+        return rec
+    valid = (y >= 0) & (y < K)
+    rec[5] += float((~valid).sum())
+    z, y = z[valid], y[valid]
+    if y.numel() == 0:
+        return rec
+    soft = (torch.nn.functional.one_hot(y, num_classes=K) - 1 / K).float()      # (frepo.soft_labels, which imports this module)
+    zy = z.gather(1, y[:, None])
+    index = torch.arange(K)[None, :]
+    rank = ((z > zy) | ((z == zy) & (index < y[:, None]))).sum(1)
+    rec[0] += float(y.numel())
+    rec[1] += ((z.double() - soft.double()) ** 2).sum()
     for slot, k in ((2, 1), (3, 3), (4, 5)):
         rec[slot] += float((rank < k).sum())
     rec[EVAL_STATS_HEAD:EVAL_STATS_HEAD + K] += torch.bincount(y[rank < 1], minlength=K).double()

@@ -19,6 +19,8 @@ The model pool and its online training, the label-margin loss, the optimiser of 
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 
 from . import hip
@@ -56,7 +58,7 @@ def nfr_pred(feat_syn: torch.Tensor, y_syn: torch.Tensor, feat_tar: torch.Tensor
 
 
 def nfr(net, x_syn: torch.Tensor, y_syn: torch.Tensor, x_tar: torch.Tensor, reg: float = 1e-6, use_flip: bool = False,
-        exact: bool = False) -> torch.Tensor:
+        exact: bool = False, feat_tar: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``PoolElement.nfr`` (distill_s2d.py:124-137) with ``weight_grad=False``: the network in eval mode with frozen parameters,
     the target clips embedded under ``no_grad`` first, the synthetic clips with the graph kept; ``use_flip`` doubles the
     synthetic set by its mirror along W.  ``x_syn`` (n, T, 3, H, W), ``y_syn`` (n, C), ``x_tar`` (m, T, 3, H, W) -> ``pred``
@@ -65,18 +67,23 @@ def nfr(net, x_syn: torch.Tensor, y_syn: torch.Tensor, x_tar: torch.Tensor, reg:
     ``exact``: both sides are multiplied by the exact weights in hi+lo pairs -- the targets through ``net.embed_exact`` (no
     dithered operand sets), the synthetic clips without the value pass that rounds the weights to the real side's format -- which
     is what the solve needs once two synthetic clips come close.  ``net.real_dither`` is afterwards as the caller
-    left it.  The default is ``embed`` on both sides, as before."""
+    left it.  The default is ``embed`` on both sides, as before.
+
+    ``feat_tar`` (m, d): the target features, embedded elsewhere (``frepo.TargetExchange``: by other ranks); ``x_tar`` is then
+    not read and may be None."""
     if use_flip:
         x_syn = torch.cat((x_syn, torch.flip(x_syn, dims=[-1])), dim=0)
         y_syn = torch.cat((y_syn, y_syn), dim=0)
     net.eval()
     if not exact:
-        with torch.no_grad():
-            feat_tar = net.embed(x_tar)
+        if feat_tar is None:
+            with torch.no_grad():
+                feat_tar = net.embed(x_tar)
         net.requires_grad_(False)
         feat_syn = net.embed(x_syn)
         return nfr_pred(feat_syn, y_syn, feat_tar, reg)
-    feat_tar = net.embed_exact(x_tar)
+    if feat_tar is None:
+        feat_tar = net.embed_exact(x_tar)
     net.requires_grad_(False)
     had, before = "real_dither" in vars(net), getattr(net, "real_dither", "auto")
     net.real_dither = True          # (the caller states that no undithered rn16 side exists: the value pass is never run)
