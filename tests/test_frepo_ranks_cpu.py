@@ -1,19 +1,14 @@
 """run_frepo's real batches from HBM, its leader / embedder protocol and its dealt evaluation, without a GPU: the index stream is
-the DataLoader's, the slices partition a batch and pad-and-trim restores it, include/vd_regress.h parses and its one name is
-declared, bound, exported and guarded, both hashes cover the new header and source, the default recipe of ``evaluate_pool`` deals
-the units as before, the driver refuses what it cannot run, and at one rank the protocol is a no-op around ``FRePoTrainer.step``."""
+the DataLoader's, the slices partition a batch and pad-and-trim restores it, the one name of include/vd_regress.h is guarded (its
+binding and hashes: tests/test_cabi.py), the default recipe of ``evaluate_pool`` deals the units as before, the driver refuses
+what it cannot run, and at one rank the protocol is a no-op around ``FRePoTrainer.step``."""
 import ctypes
 import inspect
-import os
 import random
-import re
 
 import numpy as np
 import pytest
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAME = "vdr_regress_stats"
 
 
 # ---- the index stream ----------------------------------------------------------------------------
@@ -54,30 +49,6 @@ def test_slices_partition_a_batch_and_pad_and_trim_restores_it():
     assert frepo.rank_slice(2, 0, 3) == (0, 0) and frepo.rank_slice(8, 1, 3) == (2, 5)          # an empty slice; 2 / 3 / 3
 
 
-# ---- the header and the binding ------------------------------------------------------------------
-def test_the_header_parses_and_its_name_is_declared_bound_and_exported():
-    from video_distillation_amd import hip
-    i, p = ctypes.c_int, ctypes.c_void_p
-    pinned = {NAME: (i, [p, p, i, i, p, p])}
-    assert hip.regress_signatures() == pinned
-    text = re.sub(r"/\*.*?\*/", "", open(hip.REGRESS_HEADER).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(vdr_[a-z0-9_]+)\s*\(", text))) == [NAME]
-    assert len(hip.signatures()) == 93 and not any(n.startswith("vdr_") for n in hip.EXPORTS)          # vd_hip.h stays closed
-    assert len(hip.nfr_signatures()) == 3 and len(hip.frepo_signatures()) == 2
-    with pytest.raises(ValueError, match=r"^include/vd_regress\.h: "):
-        hip.parse_header("int vd_a(int n);", "include/vd_regress.h", hip.REGRESS_NAME_PATTERN)
-    lib = hip.bind(hip.LIB_PATH if os.path.exists(hip.LIB_PATH) else hip.build())
-    fn = getattr(lib, NAME)
-    assert fn.restype is i and list(fn.argtypes) == pinned[NAME][1]
-    assert lib.vd_abi_version() == 5
-    src = open(os.path.join(ROOT, "video_distillation_amd", "csrc", "regress_stats.hip")).read()
-    assert re.findall(r'extern\s+"C"\s+\w+\s+(vdr_[a-z0-9_]+)\s*\(', src) == [NAME]
-    names = [os.path.basename(s) for s in hip.SOURCES]
-    assert names.index("regress_stats.hip") < names.index("traj.hip") and names[-1] == "traj.hip"
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "regress_signatures" in entry          # build() checks the export
-
-
 def test_argument_errors_come_back_before_any_device_call():
     """No device is present here: a call that reached HIP would not return -1, and B == 0 would not return 0."""
     from video_distillation_amd import hip
@@ -92,23 +63,6 @@ def test_argument_errors_come_back_before_any_device_call():
         assert lib.vdr_regress_stats(a, a, B, K, a, None) == -1, (B, K)
     assert lib.vdr_regress_stats(None, None, 0, 3, None, None) == 0          # B == 0 touches nothing
     assert all(v == 0.0 for v in buf)
-
-
-def test_both_hashes_cover_the_new_header_and_source(tmp_path, monkeypatch):
-    from video_distillation_amd import hip
-    want = hip.sources_hash()
-    other = tmp_path / "vd_regress.h"
-    other.write_text(open(hip.REGRESS_HEADER).read() + "\n/* touched */\n")
-    monkeypatch.setattr(hip, "REGRESS_HEADER", str(other))
-    assert hip.sources_hash() != want
-    monkeypatch.undo()
-    assert hip.sources_hash() == want
-    src = tmp_path / "regress_stats.hip"
-    src.write_text(open([s for s in hip.SOURCES if s.endswith("/regress_stats.hip")][0]).read() + "\n// touched\n")
-    monkeypatch.setattr(hip, "SOURCES", [str(src) if s.endswith("/regress_stats.hip") else s for s in hip.SOURCES])
-    assert hip.sources_hash() != want
-    monkeypatch.undo()
-    assert "REGRESS_HEADER" in inspect.getsource(hip._build_locked)
 
 
 def test_the_host_definitions_of_regress_stats_follow_the_header():

@@ -1,12 +1,11 @@
-"""Key-frame memories without a GPU: ``keyframes.table``, the argument checks and the binding of the three ``vdk_`` entry points
-(include/vd_keyframes.h), the torch expressions of expand / reduce against host loops of ``np.float32`` operations,
+"""Key-frame memories without a GPU: ``keyframes.table``, the argument checks of the three ``vdk_`` entry points
+(include/vd_keyframes.h; its binding, layout and hashes: tests/test_cabi.py), the torch expressions of expand / reduce against host loops of ``np.float32`` operations,
 ``distill.KeyframeDMTrainer`` on ``tests.cpu_backend.OracleBackend`` (K = T against ``DMTrainer`` bit for bit, three steps against
 float64 autograd, two gloo ranks against one) and ``run_dm --memories keyframes`` on the oracle backend.
 
 The host loops ``np_expand`` / ``np_reduce`` here are the bitwise reference of tests/test_gpu_keyframes.py too."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,7 +15,6 @@ from oracle import ref_cpu as R
 from tests.cpu_backend import OracleBackend
 from video_distillation_amd import checkpoint, distill, hip, keyframes, plan, run_dm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C, IPC, T, HW, PER, BATCH = 2, 2, 8, 64, 12, 8
 LR, MU, STEPS = 0.1, 0.5, 3
 SEED = 5151
@@ -186,67 +184,6 @@ def test_python_wrappers_refuse_before_the_kernel():
     with pytest.raises(ValueError, match="index outside"):
         hip.keyframe_expand(torch.zeros(2, 3, 3, 5, 7), broken)
     assert isinstance(hip.vdk_table(tab), hip.VdkTable) and hip.vdk_table(tab) is hip.vdk_table(tab)
-
-
-def test_keyframe_signatures_pinned_by_hand_and_the_93_names_stay():
-    i, q, p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
-    pinned = {
-        "vdk_table_check": (i, [p]),
-        "vdk_keyframe_expand": (i, [p, q, p, i, i, p, p]),
-        "vdk_keyframe_reduce": (i, [p, q, p, i, i, p, p]),
-    }
-    assert hip.keyframe_signatures() == pinned
-    assert len(hip.signatures()) == 93 == len(hip.EXPORTS) and not any(n.startswith("vdk_") for n in hip.EXPORTS)
-    lib = hip.lib()
-    for name, (restype, argtypes) in pinned.items():
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
-    with pytest.raises(TypeError):
-        lib.vdk_keyframe_expand(None, 1, None, 5, 7, None)          # a wrong count is an exception before the call
-    # the name pattern is an argument of the parser; each header refuses the other's names
-    text = open(hip.KEYFRAME_HEADER).read()
-    with pytest.raises(ValueError, match=r"^include/vd_hip\.h: "):
-        hip.parse_header(text)
-    assert hip.parse_header(text, "include/vd_keyframes.h", hip.KEYFRAME_NAME_PATTERN) == pinned
-    with pytest.raises(ValueError, match=r"^k\.h: "):
-        hip.parse_header("int vd_a(int n);", "k.h", hip.KEYFRAME_NAME_PATTERN)
-    assert hip.parse_header("int vd_a(int n);") == {"vd_a": (i, [i])}
-    names = [os.path.basename(s) for s in hip.SOURCES]
-    assert names[names.index("keyframes.hip") + 1] == "traj.hip" and names[-1] == "traj.hip"
-
-
-def test_table_mirror_has_the_compiler_s_layout(tmp_path):
-    fields = [(name, getattr(hip.VdkTable, name).offset, getattr(hip.VdkTable, name).size) for name, *_ in hip.VdkTable._fields_]
-    lines = ['#include <cstddef>', '#include <cstdio>', '#include "vd_keyframes.h"', 'int main() {',
-             '    std::printf("VDK_MAX_FRAMES %d\\nVdkTable %zu\\n", VDK_MAX_FRAMES, sizeof(VdkTable));']
-    for f, _, _ in fields:
-        lines.append('    std::printf("VdkTable.%s %%zu %%zu\\n", offsetof(VdkTable, %s), sizeof(((VdkTable*)0)->%s));' % (f, f, f))
-    lines += ['    return 0;', '}']
-    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = dict(line.split(None, 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    want = {"VDK_MAX_FRAMES": "%d" % hip.VDK_MAX_FRAMES, "VdkTable": "%d" % ctypes.sizeof(hip.VdkTable)}
-    for f, offset, size in fields:
-        want["VdkTable." + f] = "%d %d" % (offset, size)
-    assert got == want and ctypes.sizeof(hip.VdkTable) == 8 + 4 * 4 * 64 and keyframes.MAX_FRAMES == hip.VDK_MAX_FRAMES
-
-
-def test_new_header_and_source_are_under_the_sources_hash(tmp_path, monkeypatch):
-    want = hip.sources_hash()
-    other = tmp_path / "vd_keyframes.h"
-    other.write_text(open(hip.KEYFRAME_HEADER).read() + "\n/* touched */\n")
-    monkeypatch.setattr(hip, "KEYFRAME_HEADER", str(other))
-    assert hip.sources_hash() != want
-    monkeypatch.undo()
-    assert hip.sources_hash() == want
-    src = tmp_path / "keyframes.hip"
-    src.write_text(open([s for s in hip.SOURCES if s.endswith("/keyframes.hip")][0]).read() + "\n// touched\n")
-    monkeypatch.setattr(hip, "SOURCES", [str(src) if s.endswith("/keyframes.hip") else s for s in hip.SOURCES])
-    assert hip.sources_hash() != want
-    monkeypatch.undo()
-    hip.build()
-    assert hip.library_stamp() == want
 
 
 # ---- the torch expressions the CPU oracle backend takes --------------------------------------------------------------------

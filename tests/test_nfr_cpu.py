@@ -1,10 +1,8 @@
-"""include/vd_nfr.h and its binding without a GPU: the header parses, every ``vdn_`` name is declared, bound and exported by the
-cross-compiled library, argument errors come back before any device call, the workspace is large enough for what it carries, the
-two forms of the fp64 oracle (tests/nfr_oracle.py) agree within the bar and meet the fixture the reference's own
-``PoolElement.nfr`` wrote (tools/gen_golden.py g18), and both hashes cover the new header and source."""
+"""include/vd_nfr.h without a GPU (its binding and hashes: tests/test_cabi.py): argument errors come back before any device call,
+the workspace is large enough for what it carries, and the two forms of the fp64 oracle (tests/nfr_oracle.py) agree within the
+bar and meet the fixture the reference's own ``PoolElement.nfr`` wrote (tools/gen_golden.py g18)."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,35 +11,6 @@ import torch
 from tests import nfr_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ["vdn_nfr_backward", "vdn_nfr_forward", "vdn_nfr_workspace_bytes"]
-
-
-def test_the_header_parses_and_its_names_are_declared_bound_and_exported():
-    from video_distillation_amd import hip
-    i, q, f, p = ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
-    pinned = {
-        "vdn_nfr_workspace_bytes": (q, [i, i, i, i]),
-        "vdn_nfr_forward": (i, [p, p, p, i, i, i, i, f, p, p, p]),
-        "vdn_nfr_backward": (i, [p, p, p, i, i, i, i, f, p, p, p, p]),
-    }
-    assert hip.nfr_signatures() == pinned and sorted(pinned) == NAMES
-    text = re.sub(r"/\*.*?\*/", "", open(hip.NFR_HEADER).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(vdn_[a-z0-9_]+)\s*\(", text))) == NAMES
-    assert len(hip.signatures()) == 93 and not any(n.startswith("vdn_") for n in hip.EXPORTS)          # vd_hip.h stays closed
-    with pytest.raises(ValueError, match=r"^include/vd_nfr\.h: "):
-        hip.parse_header("int vd_a(int n);", "include/vd_nfr.h", hip.NFR_NAME_PATTERN)
-    defines = dict(re.findall(r"^[ \t]*#[ \t]*define[ \t]+(VDN_\w+)[ \t]+(\d+)[ \t]*$", text, flags=re.M))
-    assert (int(defines["VDN_MAX_SYN"]), int(defines["VDN_LDS_SYN"])) == (hip.VDN_MAX_SYN, hip.VDN_LDS_SYN) == (1024, 128)
-    if not os.path.exists(hip.LIB_PATH):
-        hip.build()
-    lib = hip.bind(hip.LIB_PATH)
-    for name, (restype, argtypes) in pinned.items():
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
-    src = open(os.path.join(ROOT, "video_distillation_amd", "csrc", "nfr.hip")).read()
-    assert sorted(re.findall(r'extern\s+"C"\s+\w+\s+(vdn_[a-z0-9_]+)\s*\(', src)) == NAMES
-    names = [os.path.basename(s) for s in hip.SOURCES]
-    assert names.index("nfr.hip") < names.index("traj.hip") and names[-1] == "traj.hip"          # (tests/test_cabi.py: traj.hip stays last)
 
 
 BAD_DIMS = [(0, 1, 1, 1), (1025, 1, 1, 1), (-1, 1, 1, 1), (4, 0, 4, 4), (4, -3, 4, 4), (4, 4, 0, 4), (4, 4, -1, 4), (4, 4, 4, 0), (4, 4, 4, -2)]
@@ -136,25 +105,6 @@ def test_closed_form_at_one_synthetic_clip():
     want = (ft.double() @ f.double().t()) / ((1.0 + reg) * float((f.double() ** 2).sum())) * y.double()
     for form in (O.by_autograd, O.by_formulas):
         assert O.rel_l2(form(f, y, ft, R, reg)[0], want) < 1e-14
-
-
-def test_both_hashes_cover_the_new_header_and_source(tmp_path, monkeypatch):
-    from video_distillation_amd import hip
-    want = hip.sources_hash()
-    other = tmp_path / "vd_nfr.h"
-    other.write_text(open(hip.NFR_HEADER).read() + "\n/* touched */\n")
-    monkeypatch.setattr(hip, "NFR_HEADER", str(other))
-    assert hip.sources_hash() != want
-    monkeypatch.undo()
-    assert hip.sources_hash() == want
-    src = tmp_path / "nfr.hip"
-    src.write_text(open([s for s in hip.SOURCES if s.endswith("/nfr.hip")][0]).read() + "\n// touched\n")
-    monkeypatch.setattr(hip, "SOURCES", [str(src) if s.endswith("/nfr.hip") else s for s in hip.SOURCES])
-    assert hip.sources_hash() != want
-    monkeypatch.undo()
-    # the per-object key (hip._build_locked) takes the header too
-    import inspect
-    assert "NFR_HEADER" in inspect.getsource(hip._build_locked)
 
 
 def test_no_file_of_the_package_imports_the_oracle():

@@ -1,5 +1,6 @@
-"""ctypes binding of libvd_hip.so.  include/vd_hip.h is the one declaration of its C ABI: every entry point's ``restype`` and
-``argtypes`` are parsed from it (``bind``), call sites pass plain Python values, a wrong count or type raises before the call.
+"""ctypes binding of libvd_hip.so.  The headers of ``HEADERS`` (include/vd_hip.h first) are the one declaration of its C ABI: every
+entry point's ``restype`` and ``argtypes`` are parsed from them (``bind``), call sites pass plain Python values, a wrong count or
+type raises before the call.
 
 PyTorch is used only as the owner of device memory and streams: every call passes
 ``tensor.data_ptr()`` and the current HIP stream handle.  There is deliberately NO fallback:
@@ -23,11 +24,15 @@ SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("conv_mfma.hip", "aux_kernel
                                                          "nfr.hip", "frepo.hip", "keyframes.hip", "traj.hip")]
 CSRC_HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("frame_norm.h", "split16.h")]      # included by more than one source: part of every hash below
 STAMP_SOURCE = os.path.join(_HERE, "csrc", "stamp.cpp")      # vd_sources_hash(): compiled on every link with the hash of SOURCES + header
-HEADER = os.path.join(_HERE, "..", "include", "vd_hip.h")
-KEYFRAME_HEADER = os.path.join(_HERE, "..", "include", "vd_keyframes.h")      # the vdk_* entry points (csrc/keyframes.hip): under both hashes too
-NFR_HEADER = os.path.join(_HERE, "..", "include", "vd_nfr.h")      # the vdn_* entry points (csrc/nfr.hip): under both hashes as well
-FREPO_HEADER = os.path.join(_HERE, "..", "include", "vd_frepo.h")      # the vdf_* entry points (csrc/frepo.hip): likewise
-REGRESS_HEADER = os.path.join(_HERE, "..", "include", "vd_regress.h")      # the vdr_* entry point (csrc/regress_stats.hip): likewise
+INCLUDE = os.path.join(_HERE, "..", "include")
+NAME_PATTERN = r"vd(?:t|s|sr)?_[a-z0-9_]+"          # include/vd_hip.h: vd_* and its three historical prefixes
+# The C ABI: (file under INCLUDE -- an absolute path stands for itself --, the pattern its function names match in full).  Parsing (``signatures``), binding
+# (``all_signatures``) and both hashes (``header_paths``) read this table and nothing else; a new header is one row here.
+HEADERS = (("vd_hip.h", NAME_PATTERN),
+           ("vd_keyframes.h", r"vdk_[a-z0-9_]+"),      # csrc/keyframes.hip
+           ("vd_nfr.h", r"vdn_[a-z0-9_]+"),      # csrc/nfr.hip
+           ("vd_frepo.h", r"vdf_[a-z0-9_]+"),      # csrc/frepo.hip
+           ("vd_regress.h", r"vdr_[a-z0-9_]+"))      # csrc/regress_stats.hip
 
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
@@ -115,6 +120,16 @@ def _file_hash(*paths: str) -> str:
     return h.hexdigest()[:16]
 
 
+def header_paths() -> list:
+    """The headers of ``HEADERS`` in table order (resolved per call: a test may replace the table)."""
+    return [os.path.join(INCLUDE, name) for name, _ in HEADERS]
+
+
+def _object_key(src: str) -> str:
+    """What one source's object file is stamped with: the source, every ABI header and the shared csrc headers."""
+    return _file_hash(src, *header_paths(), *CSRC_HEADERS)
+
+
 def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool, debug_hooks: bool) -> str:
     want = sources_hash()
     if not force and library_stamp(out) == want:
@@ -125,7 +140,7 @@ def _build_locked(out: str, objdir: str, hipcc: str, force: bool, verbose: bool,
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         side = obj + ".srchash"
         objs.append(obj)
-        key = _file_hash(src, HEADER, KEYFRAME_HEADER, NFR_HEADER, FREPO_HEADER, REGRESS_HEADER, *CSRC_HEADERS)
+        key = _object_key(src)
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
         if force or have != key:
             if os.path.exists(side):
@@ -173,21 +188,11 @@ def sources_hash() -> str:
     """sha256 (first 16 hex digits) over the kernel sources, the ABI header and the shared csrc headers: what measurement files
     that are carried from one run to the next (profiles/rNN_pmc_traffic.json -> bench.py's ``roofline.traffic``) are stamped
     with, so that a figure measured on other kernels is refused instead of quoted."""
-    import hashlib
-    h = hashlib.sha256()
-    for path in sorted(SOURCES) + [HEADER, KEYFRAME_HEADER, NFR_HEADER, FREPO_HEADER, REGRESS_HEADER] + CSRC_HEADERS:
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()[:16]
+    return _file_hash(*sorted(SOURCES), *header_paths(), *CSRC_HEADERS)
 
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
 _RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None, "const char*": ctypes.c_char_p}
-NAME_PATTERN = r"vd(?:t|s|sr)?_[a-z0-9_]+"          # include/vd_hip.h: vd_* and its three historical prefixes
-KEYFRAME_NAME_PATTERN = r"vdk_[a-z0-9_]+"          # include/vd_keyframes.h
-NFR_NAME_PATTERN = r"vdn_[a-z0-9_]+"          # include/vd_nfr.h
-FREPO_NAME_PATTERN = r"vdf_[a-z0-9_]+"          # include/vd_frepo.h
-REGRESS_NAME_PATTERN = r"vdr_[a-z0-9_]+"          # include/vd_regress.h
 _PROTOTYPE = r"(int64_t|int|void|const char\s*\*)\s*(%s)\s*\(([^()]*)\)"
 _PARAMETER = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+")
 
@@ -218,38 +223,23 @@ def parse_header(text: str, where: str = "include/vd_hip.h", names: str = NAME_P
 
 
 @functools.lru_cache(maxsize=None)
-def signatures() -> dict:
-    """{name: (restype, [argtypes])} of include/vd_hip.h, read and parsed once, when first asked for (binding a library does)."""
-    with open(HEADER) as f:
-        return parse_header(f.read())
+def signatures(header: str = "vd_hip.h") -> dict:
+    """{name: (restype, [argtypes])} of one header of ``HEADERS`` (default: include/vd_hip.h, the 93 names of ``EXPORTS``), read
+    and parsed with its own name pattern once, when first asked for (binding a library does).  ``KeyError`` for another header."""
+    names = dict(HEADERS)[header]
+    with open(os.path.join(INCLUDE, header)) as f:
+        return parse_header(f.read(), "include/" + os.path.basename(header), names)
 
 
-@functools.lru_cache(maxsize=None)
-def keyframe_signatures() -> dict:
-    """{name: (restype, [argtypes])} of include/vd_keyframes.h (the ``vdk_*`` entry points), read and parsed once."""
-    with open(KEYFRAME_HEADER) as f:
-        return parse_header(f.read(), "include/vd_keyframes.h", KEYFRAME_NAME_PATTERN)
-
-
-@functools.lru_cache(maxsize=None)
-def nfr_signatures() -> dict:
-    """{name: (restype, [argtypes])} of include/vd_nfr.h (the ``vdn_*`` entry points), read and parsed once."""
-    with open(NFR_HEADER) as f:
-        return parse_header(f.read(), "include/vd_nfr.h", NFR_NAME_PATTERN)
-
-
-@functools.lru_cache(maxsize=None)
-def frepo_signatures() -> dict:
-    """{name: (restype, [argtypes])} of include/vd_frepo.h (the ``vdf_*`` entry points), read and parsed once."""
-    with open(FREPO_HEADER) as f:
-        return parse_header(f.read(), "include/vd_frepo.h", FREPO_NAME_PATTERN)
-
-
-@functools.lru_cache(maxsize=None)
-def regress_signatures() -> dict:
-    """{name: (restype, [argtypes])} of include/vd_regress.h (the ``vdr_*`` entry point), read and parsed once."""
-    with open(REGRESS_HEADER) as f:
-        return parse_header(f.read(), "include/vd_regress.h", REGRESS_NAME_PATTERN)
+def all_signatures() -> dict:
+    """The signatures of every header of ``HEADERS``, in table order: what ``bind`` sets and a built library has to export."""
+    merged, owner = {}, {}
+    for header, _ in HEADERS:
+        for name, sig in signatures(header).items():
+            if name in merged:
+                raise ValueError("%s is declared by %s and by %s" % (name, owner[name], header))
+            merged[name], owner[name] = sig, header
+    return merged
 
 
 def __getattr__(name: str):          # hip.EXPORTS: the header's names, without reading it at import
@@ -266,11 +256,9 @@ class _Library(ctypes.CDLL):
 
 
 def bind(path: str, allow_missing: bool = False) -> ctypes.CDLL:
-    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from include/vd_hip.h,
-    include/vd_keyframes.h, include/vd_nfr.h, include/vd_frepo.h and include/vd_regress.h."""
+    """Open the library at ``path`` with every entry point's ``restype`` / ``argtypes`` set from the headers of ``HEADERS``."""
     L = _Library(path)
-    for name, (restype, argtypes) in list(signatures().items()) + list(keyframe_signatures().items()) + list(nfr_signatures().items()) \
-            + list(frepo_signatures().items()) + list(regress_signatures().items()):
+    for name, (restype, argtypes) in all_signatures().items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
