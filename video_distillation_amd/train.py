@@ -463,38 +463,50 @@ class GradMatchEngine(TrainEngine):
     def _down_sweep(self, nb: int, am, abar: torch.Tensor, x: torch.Tensor, hv: Optional[Sequence[torch.Tensor]]) -> torch.Tensor:
         """abar_l = convT(P_l^T abar_{l+1}, W_l) + convT(dz_l, V_l) from abar_3 = ``abar`` down to the pixels; with ``hv`` the
         parameter side (weight / bias adjoints of the three conv levels) is accumulated into hv[0..5]."""
-        eng, geo, st = self.eng, self.geo, hip.stream_ptr(self.device)
-        _, n1, n2, _, act1, act2, gbar1, gbar2 = self._sweep_bufs(nb)
+        geo = self.geo
         dx = torch.empty((nb, geo.frames, geo.channel, geo.height, geo.width), dtype=torch.float32, device=self.device)
         grad, layout = abar, 0
         for li in (2, 1, 0):
-            cout, To, Ho, Wo = eng.dims[li][1], *eng.dims[li][8:11]
-            dy = eng.dy_buf(li, nb)       # dz_l of the first-order pass
-            inv_dv = inv_gd = None
-            if self.scaled:
-                # dy_l carries the first-order pass's scale of this level (gscale%d of TrainEngine.feat_backward, kept in the
-                # step's workspace), V_l and gbar_l the scales of the upward sweep; zb_l = P_l^T abar_{l+1} gets its own (zscale%d)
-                gs = eng.scale_buf("gscale%d" % li)
-                inv_dv = self._combine(gs, self._sv[li], 0, "dvscale%d" % li)[1:]
-                if hv and li > 0:
-                    inv_gd = self._combine(gs, self._sg[li], 0, "gdscale%d" % li)[1:]
-            zb, nslots, _, inv_z = eng.level_unpool(li, nb, grad, layout, am[li], name="zb", scale_name="zscale")
-            out = dx if li == 0 else eng.dx_buf(li, nb, "ax")
-            eng.level_dgrad(eng.bwd[li], zb, nslots, out, nb, inv_z)
-            eng.level_dgrad(self.bwdV[li], dy, nslots, out, nb, inv_dv)   # (accumulates on top of the stores above)
-            if hv:
-                # parameter side: z_l = conv(a_l, W_l) + b_l carries zbar_l, and g_{a_l} = convT(dz_l, W_l) carries gbar_l
-                op = self._wgrad(li, nb)
-                hip.run("vd_bias_grad_pooled", hip.ptr(grad), hip.ptr(am[li]), nb, cout, To * Ho * Wo, layout,
-                        hip.ptr(hv[2 * li + 1]), st)
-                if li == 0:
-                    op.run(x, True, 0, zb, nslots, hv[0], out_scale=inv_z)
-                else:
-                    a_l, g_l, n_l = (act1, gbar1, n1) if li == 1 else (act2, gbar2, n2)
-                    op.run(a_l, False, n_l, zb, nslots, hv[2 * li], out_scale=inv_z)
-                    op.run(g_l, False, n_l, dy, nslots, hv[2 * li], out_scale=inv_gd)
-            grad, layout = out, 1
+            grad, layout = self.down_level(li, nb, grad, layout, am[li], x, hv, out=dx if li == 0 else None), 1
         return dx
+
+    def down_level(self, li: int, nb: int, grad: torch.Tensor, layout: int, am_l: torch.Tensor, x: torch.Tensor,
+                   hv: Optional[Sequence[torch.Tensor]], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One level of the downward sweep on the current stream: abar_l from the POOLED incoming adjoint ``grad`` (``layout`` /
+        arg-max bytes ``am_l`` as vd_unpool_relu_bwd takes them) and the workspace state the sweeps before it left (dz_l and its
+        scale, the packed operands and scales of ``_pack_adjoint``, the tangent and scale of ``_up_sweep``, the source slots);
+        with ``hv`` the level's weight / bias adjoints are accumulated into hv[2 li], hv[2 li + 1].  -> abar_l (the pixel
+        gradient at level 0), written into ``out`` when given."""
+        eng, st = self.eng, hip.stream_ptr(self.device)
+        _, n1, n2, _, act1, act2, gbar1, gbar2 = self._sweep_bufs(nb)
+        cout, To, Ho, Wo = eng.dims[li][1], *eng.dims[li][8:11]
+        dy = eng.dy_buf(li, nb)       # dz_l of the first-order pass
+        inv_dv = inv_gd = None
+        if self.scaled:
+            # dy_l carries the first-order pass's scale of this level (gscale%d of TrainEngine.feat_backward, kept in the
+            # step's workspace), V_l and gbar_l the scales of the upward sweep; zb_l = P_l^T abar_{l+1} gets its own (zscale%d)
+            gs = eng.scale_buf("gscale%d" % li)
+            inv_dv = self._combine(gs, self._sv[li], 0, "dvscale%d" % li)[1:]
+            if hv and li > 0:
+                inv_gd = self._combine(gs, self._sg[li], 0, "gdscale%d" % li)[1:]
+        zb, nslots, _, inv_z = eng.level_unpool(li, nb, grad, layout, am_l, name="zb", scale_name="zscale")
+        if out is None:
+            out = eng.dx_buf(li, nb, "ax") if li else torch.empty(
+                (nb, self.geo.frames, self.geo.channel, self.geo.height, self.geo.width), dtype=torch.float32, device=self.device)
+        eng.level_dgrad(eng.bwd[li], zb, nslots, out, nb, inv_z)
+        eng.level_dgrad(self.bwdV[li], dy, nslots, out, nb, inv_dv)   # (accumulates on top of the stores above)
+        if hv:
+            # parameter side: z_l = conv(a_l, W_l) + b_l carries zbar_l, and g_{a_l} = convT(dz_l, W_l) carries gbar_l
+            op = self._wgrad(li, nb)
+            hip.run("vd_bias_grad_pooled", hip.ptr(grad), hip.ptr(am_l), nb, cout, To * Ho * Wo, layout,
+                    hip.ptr(hv[2 * li + 1]), st)
+            if li == 0:
+                op.run(x, True, 0, zb, nslots, hv[0], out_scale=inv_z)
+            else:
+                a_l, g_l, n_l = (act1, gbar1, n1) if li == 1 else (act2, gbar2, n2)
+                op.run(a_l, False, n_l, zb, nslots, hv[2 * li], out_scale=inv_z)
+                op.run(g_l, False, n_l, dy, nslots, hv[2 * li], out_scale=inv_gd)
+        return out
 
     def _views(self, n_tensors: int):
         return self._split(torch.zeros(sum(self.sizes[:n_tensors]), dtype=torch.float32, device=self.device), n_tensors)
