@@ -54,6 +54,11 @@ extern "C" {
                                 of every box type of a VD_PREC_F16C8 program follow S / 4 TILE SKIP MASKS: bit i of word g = M tile i
                                 takes no part in K steps 4 g .. 4 g + 3 (its taps lie outside the input grid) */
 
+/* VdConvParams.persist: the generations count in the low 16 bits, one option bit each above (decimal: hip.py mirrors them) */
+#define VD_PERSIST_GENS_MASK 65535     /* 0xFFFF */
+#define VD_PERSIST_PLAIN_K   524288    /* bit 19: the plain K loop of vd_conv0_breg */
+#define VD_PERSIST_NO_ALT    1048576   /* bit 20: no sign alternation of a hi+lo program's accumulation */
+
 /* One tile program (see video_distillation_amd/plan.py).  All pointers are device
  * pointers; strides are in the units given. */
 typedef struct VdConvParams {
@@ -95,11 +100,12 @@ typedef struct VdConvParams {
     int32_t NTW;                  /* N tiles per wave (0/1: one; 2: an A fragment feeds two MFMAs; wave columns = NT / NTW) */
     const int64_t* clip_index;    /* first-layer programs (ncl = 1): source clip of batch clip b is src + clip_index[b]*clip stride (NULL: b) */
     int32_t mt_valid;             /* NTW = 2: M tiles per box that carry rows (< MW*MTW: the last wave row skips its padding tile); 0 = all */
-    int32_t persist;              /* 0: one workgroup per box; g>0: each workgroup walks boxes so that the grid is g generations of resident workgroups;
-                                     vd_conv0_breg: bit 19 = run a frame-tile program (pair_flip != 0) with the plain K loop (one LDS read per
-                                     MFMA) instead of the frame-sharing one (A/B measurements; bitwise the same results);
-                                     bit 20 (hi+lo formats) = do NOT alternate the accumulation's sign per channel chunk: the matrix instruction rounds
-                                     with a bias toward minus infinity (1.4 ulp per 600 v_mfma_f32_32x32x16_f16, whatever the sign), coherent over
+    int32_t persist;              /* persist & VD_PERSIST_GENS_MASK = 0: one workgroup per box; g>0: each workgroup walks boxes so that the grid is
+                                     g generations of resident workgroups.  The bits above are options of single programs:
+                                     VD_PERSIST_PLAIN_K (vd_conv0_breg only) = run a frame-tile program (pair_flip != 0) with the plain K loop (one LDS
+                                     read per MFMA) instead of the frame-sharing one (A/B measurements; bitwise the same results);
+                                     VD_PERSIST_NO_ALT (hi+lo formats) = do NOT alternate the accumulation's sign per channel chunk: the matrix instruction
+                                     rounds with a bias toward minus infinity (1.4 ulp per 600 v_mfma_f32_32x32x16_f16, whatever the sign), coherent over
                                      all outputs of a launch; by default a hi+lo program negates its accumulators at every chunk boundary and flips
                                      the sign of odd chunks' B fragments, which makes the bias zero-mean (sums over 1e8 outputs: 1e-5 -> 1e-6) */
     uint64_t* stamps;             /* dbg bit 3: [grid][8] s_memtime stamps of workgroup phases  */

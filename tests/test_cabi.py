@@ -435,6 +435,8 @@ def test_constants_mirrored_by_hand_equal_the_header_s_defines():
     assert hip.PREC == {name[len("VD_PREC_"):].lower(): v for name, v in defines.items() if name.startswith("VD_PREC_")}
     assert len(hip.PREC) == 5 and sorted(hip.PREC.values()) == [0, 1, 2, 3, 4]
     assert hip.F16X3_WSHIFT == defines["VD_F16X3_WSHIFT"]
+    assert (hip.PERSIST_GENS_MASK, hip.PERSIST_PLAIN_K, hip.PERSIST_NO_ALT) == (0xFFFF, 1 << 19, 1 << 20) == tuple(
+        defines["VD_PERSIST_" + name] for name in ("GENS_MASK", "PLAIN_K", "NO_ALT"))
     assert hip.VD_PACK_MAX == defines["VD_PACK_MAX"] and hip.VD_MATCH_MAX_SEG == defines["VD_MATCH_MAX_SEG"]
     assert hip.CORESET_METHOD == {"herding": defines["VD_CORESET_HERDING"], "k-center": defines["VD_CORESET_KCENTER"]}
     assert defines["VD_ABI_VERSION"] == 5

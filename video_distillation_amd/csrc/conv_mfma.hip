@@ -281,15 +281,6 @@ __device__ __forceinline__ void conv_mfma_body(const VdConvParams& p, const int 
             grp = bid - bi * ngrp;
         }
     }
-    if constexpr (C8) {
-        // position-tile programs, persist bit 19: WINDOW-major box order -- with the XCD-contiguous ranges above an XCD then works on
-        // one pool window, i.e. streams ONE of the program's packed B operand sets through its L2 instead of all of them
-        if (p.persist & 0x80000) {
-            const int ngrp = total_boxes / p.nbox;
-            bi = bid / ngrp;
-            grp = bid - bi * ngrp;
-        }
-    }
     const int clip0 = grp * p.ncl;
 
     // (1) the gather entries of this wave's DMA groups: the longest dependent chain of the prologue,
@@ -347,7 +338,7 @@ __device__ __forceinline__ void conv_mfma_body(const VdConvParams& p, const int 
         //  clip -- the dithered weights of the real side, distill.HipBackend.embed_pool)
         // (the sign flip is applied where a fragment is USED, a step or two after its load was issued: flipped at the load it would have to
         //  land at once -- the B prefetch ring would be gone, measured -7 .. -10 % on the hi+lo programs.  persist bit 20: alternation off, A/B)
-        const bool alt_on = ALT && !(p.persist & 0x100000);
+        const bool alt_on = ALT && !(p.persist & VD_PERSIST_NO_ALT);
         if constexpr (ALT) {
             if (alt_on && ph == 0 && cc > 0) {
 #pragma unroll
@@ -827,7 +818,7 @@ __device__ __forceinline__ void conv_mfma_body(const VdConvParams& p, const int 
     }
 
     if constexpr (ALT) {            // an even number of chunks leaves -sum in the accumulators
-        if (!(p.persist & 0x100000) && !(p.CC & 1)) {
+        if (!(p.persist & VD_PERSIST_NO_ALT) && !(p.CC & 1)) {
 #pragma unroll
             for (int i = 0; i < TILES; ++i)
 #pragma unroll
@@ -1521,11 +1512,11 @@ extern "C" int vd_conv0_breg(const VdConvParams* pp, void* stream) {
         return -2;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     VdConvParams q = p;
-    q.persist = p.persist & 0xFFFF;
+    q.persist = p.persist & VD_PERSIST_GENS_MASK;
     // frame-tile programs (pair_flip != 0; plan.plan_forward_pix): the K loop that reads every A fragment once for all the tiles
     // it serves, unless persist bit 19 asks for the plain one (A/B measurements, bitwise the same results)
     // (the frame-sharing loop carries the LDS pitches of the 4 x 8 x 8 box as instruction offsets: pair_flip bits 8..15 / 16..31)
-    const bool fs = (p.pair_flip & 0xF) != 0 && (p.pair_flip >> 8) == (9 | (189 << 8)) && !(p.persist & 0x80000);
+    const bool fs = (p.pair_flip & 0xF) != 0 && (p.pair_flip >> 8) == (9 | (189 << 8)) && !(p.persist & VD_PERSIST_PLAIN_K);
     if (p.prec == VD_PREC_F16) return fs ? launch_conv0_breg<VD_PREC_F16, true>(q, st) : launch_conv0_breg<VD_PREC_F16, false>(q, st);
     if (p.prec == VD_PREC_BF16) return fs ? launch_conv0_breg<VD_PREC_BF16, true>(q, st) : launch_conv0_breg<VD_PREC_BF16, false>(q, st);
     return -2;
@@ -1557,7 +1548,7 @@ static int launch(const VdConvParams& p, hipStream_t st) {
     if (occ < 1) occ = 1;
     // a few workgroup "generations" keep the tail short while still amortising the dispatch
     const int64_t slots = (int64_t)ncu * occ;
-    const int gens = p.persist & 0xFFFF;          // (the bits above are options of single programs)
+    const int gens = p.persist & VD_PERSIST_GENS_MASK;          // (the bits above are options of single programs)
     int per = (gens > 0 && MTW * NTW <= 4) ? (int)((total + slots * gens - 1) / (slots * gens)) : 1;
     if (per < 1) per = 1;
     const int64_t grid = (total + per - 1) / per;

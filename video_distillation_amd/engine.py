@@ -42,6 +42,7 @@ class _DevPlan:
         planes = 2 if hip.is_x3(prec) else 1
         self.prec = prec
         self.wpk = self._new_wpk(planes, device)
+        self.scales = self._new_scales(device)             # VD_PREC_F16C8 programs: the scale table of pack_c8 (None elsewhere)
         self.wpk_d: Optional[torch.Tensor] = None          # dithered operand sets (pack_dither)
         self.range_stats: Optional[torch.Tensor] = None    # emit_lo = 2 launches: [saturated outputs, float bits of max |output|] (vd_hip.h)
         self._slots: Dict[int, tuple] = {}                 # buffer sets of use_slot()
@@ -64,7 +65,7 @@ class _DevPlan:
         p.ntypes = len(plan.types)
         p.persist = P.BOX_WALK_GENERATIONS
         if os.environ.get("VD_NO_ALT") == "1":       # A/B: hi+lo programs without the per-chunk sign alternation of their accumulation (conv_mfma.hip ALT)
-            p.persist |= 0x100000
+            p.persist |= hip.PERSIST_NO_ALT
         p.tab_ofs[0], p.tab_ofs[1], p.tab_ofs[2] = int(desc[0][7]), int(desc[0][8]), int(desc[0][9])
         self.zero = torch.zeros(64, dtype=torch.uint8, device=device)
         p.zero_slot = self.zero.data_ptr()
@@ -95,14 +96,17 @@ class _DevPlan:
             torch.empty(planes * self.n_w, dtype=torch.int16, device=device)
         return flat[:planes * self.n_w].view(planes, self.n_w)
 
+    def _new_scales(self, device) -> Optional[torch.Tensor]:
+        return torch.zeros(8, dtype=torch.float32, device=device) if self.prec == hip.PREC["f16c8"] else None
+
     def use_slot(self, k: int) -> None:
-        """Switch to the k-th set of packed-operand buffers (``wpk`` and the dithered sets ``wpk_d``), allocated on first use.  Two
-        sets let the operands of step i + 1 be packed on a side stream while the launches of step i still read theirs
+        """Switch to the k-th set of packed-operand buffers (``wpk``, the dithered sets ``wpk_d`` and the fp8 ``scales``), allocated on
+        first use.  Two sets let the operands of step i + 1 be packed on a side stream while the launches of step i still read theirs
         (EmbedEngine.set_weights(slot=), distill.DMTrainer)."""
-        self._slots[self._slot] = (self.wpk, self.wpk_d)
+        self._slots[self._slot] = (self.wpk, self.wpk_d, self.scales)
         if k not in self._slots:
-            self._slots[k] = (self._new_wpk(self.wpk.shape[0], self.wpk.device), None)
-        self.wpk, self.wpk_d = self._slots[k]
+            self._slots[k] = (self._new_wpk(self.wpk.shape[0], self.wpk.device), None, self._new_scales(self.wpk.device))
+        self.wpk, self.wpk_d, self.scales = self._slots[k]
         self._slot = k
 
     def pack(self, w: torch.Tensor) -> None:
@@ -114,14 +118,14 @@ class _DevPlan:
         hip.run("vd_pack_weights", hip.ptr(w), hip.ptr(self.widx), self.n_w, hip.ptr(self.wpk[0]), hip.ptr(lo), self.prec,
                 hip.stream_ptr(w.device))
 
-    def pack_c8(self, w: torch.Tensor, scales: torch.Tensor) -> None:
+    def pack_c8(self, w: torch.Tensor) -> None:
         """Operand planes of a VD_PREC_F16C8 program (vd_pack_weights_c8): fp16 fragments + the fp8 fragments of W_hi and W_lo;
-        ``scales`` (>= 6 floats of device scratch) receives the two E8M0 codes ``run(..., out_scale=scales)`` hands to the kernel."""
-        assert w.dtype == torch.float32 and w.is_contiguous() and self.wpk.shape[0] == 2
+        ``self.scales`` receives the two E8M0 codes ``run(..., out_scale=self.scales)`` hands to the kernel."""
+        assert w.dtype == torch.float32 and w.is_contiguous() and self.wpk.shape[0] == 2 and self.scales is not None
         pl = self.plan
         sets = self.n_w // (pl.CC * pl.S * pl.NT * 512)       # (position-tile programs: one operand set per box, chunk-major inside)
         hip.run("vd_pack_weights_c8", hip.ptr(w), w.numel(), hip.ptr(self.widx), sets * pl.CC, pl.S, pl.NT, hip.ptr(self.wpk[0]),
-                hip.ptr(self.wpk[1]), hip.ptr(scales), hip.stream_ptr(w.device))
+                hip.ptr(self.wpk[1]), hip.ptr(self.scales), hip.stream_ptr(w.device))
 
     def pack_dither(self, w: torch.Tensor, groups: int) -> None:
         """``groups`` dithered single-pass operand sets (vd_pack_weights_dither); ``run(..., group=g)`` multiplies by set g."""
@@ -134,12 +138,12 @@ class _DevPlan:
     def run(self, src: torch.Tensor, src_plane_slots: int, bias: Optional[torch.Tensor], dst_ptr: int,
             dst_plane_stride: int, argmax: Optional[torch.Tensor], nclips: int, out_scale: Optional[torch.Tensor] = None,
             wpk: Optional[torch.Tensor] = None, w_plane_elems: int = 0, clip_index: Optional[torch.Tensor] = None,
-            group: Optional[int] = None, set_clips: int = 0, emit_lo: bool = False, launch: bool = True) -> None:
+            group: Optional[int] = None, set_clips: int = 0, emit_lo: int = 0, launch: bool = True) -> None:
         """``launch=False`` only fills the parameter block (``run_together`` then sends several programs out as one launch)."""
         p = self.params
-        p.emit_lo = int(emit_lo)        # single-pass program, staged pooled epilogue: 1 = also write the fp16 low plane (dst_plane_stride
+        p.emit_lo = emit_lo             # single-pass program, staged pooled epilogue: 1 = also write the fp16 low plane (dst_plane_stride
         #                                 behind), 2 = write fp8 low parts there instead (for a VD_PREC_F16C8 consumer)
-        if int(emit_lo) == 2:      # ... whose fixed scalings hold for a RANGE of output magnitudes: the launch records what it saw
+        if emit_lo == 2:           # ... whose fixed scalings hold for a RANGE of output magnitudes: the launch records what it saw
             if self.range_stats is None:
                 self.range_stats = torch.zeros(2, dtype=torch.int32, device=src.device)
             p.range_stats = self.range_stats.data_ptr()
@@ -171,7 +175,7 @@ class _DevPlan:
         if self.breg_ok and argmax is None and (not p.dbg or os.environ.get("VD_BREG_DBG") == "1"):
             persist = p.persist
             if self.breg_variant == 4:
-                p.persist = persist | 0x80000          # (VdConvParams.persist bit 19: the plain K loop on a frame-tile program)
+                p.persist = persist | hip.PERSIST_PLAIN_K          # (the plain K loop on a frame-tile program)
             try:
                 hip.run("vd_conv0_breg", ctypes.byref(p), hip.stream_ptr(src.device), what="vd_conv0_breg(%s)" % self.plan.name)
             finally:
@@ -315,12 +319,14 @@ def clip_slots(geo: P.NetGeometry, fwd_plans: Sequence[P.ConvPlan]) -> Tuple[int
 class EmbedEngine:
     def __init__(self, geo: P.NetGeometry, prec: str = "bf16x3", device="cuda:0", chunk: int = 256,
                  prec_bwd: Optional[str] = None, ntw0: Optional[int] = None, batch_hint: Optional[int] = None,
-                 last_hilo: bool = False, bwd0_small: bool = False):
-        """``last_hilo`` (single-pass engines, forward without kept arg-max): the LAST conv level runs in the hi+lo format of the
-        same 16-bit type -- level 1's program also writes the low plane of its pooled outputs (VdConvParams.emit_lo) and level 2
+                 last_hilo=False, bwd0_small: bool = False):
+        """``last_hilo`` = True (single-pass engines, forward without kept arg-max): the LAST conv level runs in the hi+lo format of
+        the same 16-bit type -- level 1's program also writes the low plane of its pooled outputs (VdConvParams.emit_lo) and level 2
         multiplies hi+lo activations by hi+lo weights (3 MFMAs per product on 5.6 % of the network's FLOPs).  That removes two
         of the six rounding sources of a single-pass forward (level 1's output rounding, level 2's weight rounding; DESIGN
-        section 2, tests/sim_error_budget_tool.py)."""
+        section 2, tests/sim_error_budget_tool.py).  ``last_hilo`` = "c8" (f16 only): that level as VD_PREC_F16C8, the two correction
+        products on the fp8 matrix instruction; level 1 then emits fp8 low parts instead of the fp16 low plane.  ValueError where
+        the geometry has no such program.  Kept as ``self.last`` = "x1" / "x3" / "c8"."""
         if not torch.cuda.is_available():
             raise RuntimeError("EmbedEngine needs a HIP device (no CPU fallback)")
         hip.lib()
@@ -342,55 +348,17 @@ class EmbedEngine:
         self.dims = net["dims"]
         self.per0, self.per1, self.per2 = clip_slots(geo, net["fwd"])
         self.fwd = [_DevPlan(pl, self.device, self.prec) for pl in net["fwd"]]
+        # the LAST level's form: "x1" = the single-pass program fwd[2]; "x3" / "c8" = the hi+lo program ``fwd2x`` (plan.plan_last_level),
+        # for which level 1 also writes a low plane (VdConvParams.emit_lo: 1 = fp16 low parts, 2 = the fp8 planes of a "c8" consumer)
+        self.last = "c8" if last_hilo == "c8" else "x3" if last_hilo else "x1"
+        self.last_c8 = self.last == "c8"
+        self._emit_lo = {"x1": 0, "x3": 1, "c8": 2}[self.last]
         self.fwd2x = None
-        self.last_c8 = False
-        self._c8_scale_slots: Dict[int, torch.Tensor] = {}    # set_weights(slot=): the fp8-corrected program's scale table per buffer set
-        if last_hilo:
+        if self.last != "x1":
             if hip.is_x3(self.prec):
                 raise ValueError("last_hilo is an option of the single-pass formats (%s already carries hi+lo planes)" % prec)
-            import dataclasses
-            pl2 = net["fwd"][2]
-            if pl2.NTW == 2 and pl2.MTW == 4 and pl2.ncl % 2 == 0:
-                # The hi+lo program keeps two operand planes of its patch in LDS: with the single-pass program's boxes (two clips, 4 M
-                # tiles x 2 N tiles per wave, 2 x 58 KB) only one workgroup fits a CU.  One clip per box (4 M tiles x 1 N tile per
-                # wave, 2 x 29 KB) lets two share it: 0.74 -> 0.68 ms per 512 clips, 4.53 -> 4.27 ms per launch in the bench (same
-                # box); same K order per output, bitwise the same features.
-                d2 = self.dims[2]
-                try:
-                    alt = P.plan_forward_cl("fwd2", d2[0], d2[1], d2[2], d2[3], d2[4], d2[11], feat_out=True, ntw=1, mtw_options=(4,),
-                                            step_multiple=4 if last_hilo == "c8" else 1)
-                    if alt.rows_total <= pl2.rows_total and 2 * alt.gather_table().shape[1] * 16 <= 72 * 1024:
-                        pl2 = alt
-                except ValueError:
-                    pass
-            # ``last_hilo == "c8"`` (f16 only): the last level as VD_PREC_F16C8 -- fp16 main product, the two hi+lo correction products
-            # on the block-scaled fp8 matrix instruction once per four K steps (two MFMA-equivalents per product instead of three);
-            # level 1 then emits fp8 low parts (emit_lo = 2) instead of the fp16 low plane.  Needs the one-clip 4 x 1-tile program.
-            self.last_c8 = (last_hilo == "c8")
-            if self.last_c8:
-                # POSITION TILES (plan.plan_forward_pos): rows = (clip, frame) pairs of one output position, so that the taps outside
-                # the input grid -- half of them at 7 x 7, two thirds at 4 x 4 -- are skipped per tile; VD_C8_POS=0 keeps the
-                # row-major program, which needs the one-clip 4 x 1-tile decomposition (not every geometry has it)
-                d2 = self.dims[2]
-                pos = None
-                if prec == "f16" and os.environ.get("VD_C8_POS", "1") == "1":
-                    try:
-                        pos = P.plan_forward_pos("fwd2_pos", d2[0], d2[1], d2[2], d2[3], d2[4], d2[11])
-                    except (ValueError, AssertionError):
-                        pos = None
-                if pos is not None:
-                    pl2 = pos
-                elif prec == "f16" and pl2.NTW == 1 and pl2.MTW == 4 and pl2.S % 4 == 0:
-                    pl2 = P.with_skip_table(dataclasses.replace(pl2, types=[dataclasses.replace(t) for t in pl2.types]))
-                else:
-                    raise ValueError("last_hilo='c8' needs the f16 format and either position tiles (frames dividing 32) or the one-clip "
-                                     "4 x 1-tile last-level program (geometry %s)" % (geo,))
-            self.fwd2x = _DevPlan(dataclasses.replace(pl2, name="fwd2_c8" if self.last_c8 else "fwd2_hilo"), self.device,
-                                  hip.PREC["f16c8"] if self.last_c8 else hip.PREC[prec + "x3"])
-            if self.last_c8:
-                self.c8_scales = torch.zeros(8, dtype=torch.float32, device=self.device)
-                if pl2.epi == P.EPI_POS_FEAT and os.environ.get("VD_C8_BOXMAJOR", "0") == "1":
-                    self.fwd2x.params.persist |= 0x80000       # window-major box order (VdConvParams.persist bit 19)
+            self.fwd2x = _DevPlan(P.plan_last_level(self.dims, net["fwd"][2], self.last, prec), self.device,
+                                  hip.PREC["f16c8" if self.last_c8 else prec + "x3"])
         # operand precision of the input-gradient passes (default: same as the forward)
         self.prec_bwd = hip.PREC[prec_bwd] if prec_bwd else self.prec
         self.planes_bwd = 2 if hip.is_x3(self.prec_bwd) else 1
@@ -399,6 +367,8 @@ class EmbedEngine:
         self._weights: Optional[List[torch.Tensor]] = None
         self._bwd_packed = False
         self._ws: Dict[str, torch.Tensor] = {}
+        self._dither = 0                  # dithered operand sets of the latest set_weights(dither=G)
+        self.after_first_level = None     # called behind the first level's launch of forward_sets (distill.DMTrainer records an event)
         self.profile = None   # list -> (layer, clips, start_event, end_event) per forward launch
 
     # ------------------------------------------------------------------------------------
@@ -452,15 +422,11 @@ class EmbedEngine:
         if slot is not None:      # (forward operands only: the packed buffers of slot ``slot``; the launches that follow read them)
             for dp in self.fwd + ([self.fwd2x] if self.fwd2x is not None else []):
                 dp.use_slot(slot)
-            if self.last_c8:
-                if slot not in self._c8_scale_slots:
-                    self._c8_scale_slots[slot] = torch.zeros(8, dtype=torch.float32, device=self.device)
-                self.c8_scales = self._c8_scale_slots[slot]
         with batched_packs():
             for li in range(3):
                 if li == 2 and self.fwd2x is not None:      # the last level multiplies by the exact hi+lo weights: nothing to dither
                     if self.last_c8:
-                        self.fwd2x.pack_c8(ws[4], self.c8_scales)
+                        self.fwd2x.pack_c8(ws[4])
                     else:
                         self.fwd2x.pack(ws[4])
                     continue
@@ -495,6 +461,19 @@ class EmbedEngine:
                     hip.ptr(lo), self.prec, st)
         return rows
 
+    def _launch(self, li: int, src: torch.Tensor, src_plane_slots: int, dst_ptr: int, dst_plane_stride: int,
+                argmax: Optional[torch.Tensor], nclips: int, group: Optional[int] = None, set_clips: int = 0,
+                clip_index: Optional[torch.Tensor] = None) -> None:
+        """Level ``li`` of the forward over ``nclips`` clips of ``src``: its program, bias, and what the last level's form asks of
+        it -- level 1 of an "x3" / "c8" engine also writes the low plane, level 2 then runs the hi+lo program, whose exact weights
+        are ONE operand set (the caller's ``group`` / ``set_clips`` selection does not apply) and which brings its scale table."""
+        bias = self._weights[2 * li + 1]
+        if li == 2 and self.fwd2x is not None:
+            self.fwd2x.run(src, src_plane_slots, bias, dst_ptr, dst_plane_stride, argmax, nclips, out_scale=self.fwd2x.scales)
+        else:
+            self.fwd[li].run(src, src_plane_slots, bias, dst_ptr, dst_plane_stride, argmax, nclips, clip_index=clip_index, group=group,
+                             set_clips=set_clips, emit_lo=self._emit_lo if li == 1 else 0)
+
     def forward(self, x: torch.Tensor, keep: bool = False, index: Optional[torch.Tensor] = None,
                 rows: Optional[torch.Tensor] = None, group: Optional[int] = None, stills: Optional[torch.Tensor] = None):
         """x (B,T,3,H,W) fp32 on the device -> features (B, num_feat) fp32.  With ``keep`` the
@@ -504,7 +483,7 @@ class EmbedEngine:
         ``stills`` (N,3,H,W) with ``index`` (``x`` None): the batch is the still clips stills[index[b]] repeated over the frames;
         their first-level rows are written straight from the images (vdsr_still_rows), everything after is the clips' path."""
         assert self._weights is not None, "set_weights() first"
-        assert group is None or 0 <= group < getattr(self, "_dither", 0), "set_weights(dither=G) first"
+        assert group is None or 0 <= group < self._dither, "set_weights(dither=G) first"
         g = self.geo
         if stills is not None:
             assert x is None and rows is None and index is not None, "stills: a pool of images and an index, nothing else"
@@ -535,7 +514,7 @@ class EmbedEngine:
                     hip.run("vd_pix2rows", hip.ptr(xin), hip.ptr(None if index is None else index[c0:]), nb, g.frames, g.height,
                             g.width, hip.ptr(slots0[0]), hip.ptr(lo), self.prec, st)
             n1, n2 = nb * self.per1, nb * self.per2
-            hilo = self.fwd2x is not None
+            hilo = self.last != "x1"
             assert not (hilo and keep), "last_hilo engines have no kept-arg-max forward"
             act1, act2 = self.act_bufs(nb, 2 if hilo else None)
             am0 = am1 = am2 = None
@@ -543,18 +522,14 @@ class EmbedEngine:
                 am0 = torch.empty(n1 * 8, dtype=torch.uint8, device=self.device)
                 am1 = torch.empty(n2 * 8, dtype=torch.uint8, device=self.device)
                 am2 = torch.empty(nb * self.num_feat, dtype=torch.uint8, device=self.device)
-            w = self._weights
             prof = self.profile
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if prof is not None else None
             if ev: ev[0].record()
-            self.fwd[0].run(slots0, n_slots0, w[1], act1.data_ptr(), n1, am0, nb, clip_index=cidx, group=group)
+            self._launch(0, slots0, n_slots0, act1.data_ptr(), n1, am0, nb, group=group, clip_index=cidx)
             if ev: ev[1].record()
-            self.fwd[1].run(act1, n1, w[3], act2.data_ptr(), n2, am1, nb, group=group, emit_lo=(2 if self.last_c8 else 1) if hilo else 0)
+            self._launch(1, act1, n1, act2.data_ptr(), n2, am1, nb, group=group)
             if ev: ev[2].record()
-            if hilo:
-                self.fwd2x.run(act2, n2, w[5], feats[c0:].data_ptr(), 0, None, nb, out_scale=self.c8_scales if self.last_c8 else None)
-            else:
-                self.fwd[2].run(act2, n2, w[5], feats[c0:].data_ptr(), 0, am2, nb, group=group)
+            self._launch(2, act2, n2, feats[c0:].data_ptr(), 0, am2, nb, group=group)
             if ev:
                 ev[3].record()
                 prof += [("fwd0", nb, ev[0], ev[1]), ("fwd1", nb, ev[1], ev[2]), ("fwd2", nb, ev[2], ev[3])]
@@ -583,7 +558,7 @@ class EmbedEngine:
         multiplying by dithered operand set s (single-pass engines): ONE launch per layer, the set picked per box from the clip
         number (VdConvParams.w_set_clips; the first layer's register-resident-B kernel reloads its fragments when a
         workgroup's walk crosses into the next block).  ``stills`` (``x`` None): as in ``forward``."""
-        G = getattr(self, "_dither", 0)
+        G = self._dither
         B = int(index.numel())
         assert G >= 2 and B % G == 0 and self.planes == 1, "set_weights(dither=G) on a single-pass engine first"
         g = self.geo
@@ -592,9 +567,8 @@ class EmbedEngine:
         feats = torch.empty((B, self.num_feat), dtype=torch.float32, device=self.device)
         per0, per1, per2 = self.per0, self.per1, self.per2
         n_slots0, n1, n2 = B * per0, B * per1, B * per2
-        hilo = self.fwd2x is not None
+        hilo = self.last != "x1"
         act1, act2 = self.act_bufs(B, 2 if hilo else None)
-        w = self._weights
         if stills is not None:
             assert x is None and rows is None, "stills: a pool of images and an index, nothing else"
             slots0 = self.rows_buf(B)
@@ -605,29 +579,25 @@ class EmbedEngine:
                     g.width, hip.ptr(slots0[0]), hip.ptr(None), self.prec, hip.stream_ptr(self.device))
         if self.fwd[0].breg_ok:       # register-resident-B kernel: reloads its fragments when a workgroup's walk crosses into the next set
             if rows is not None:
-                self.fwd[0].run(rows, int(rows.shape[1]), w[1], act1.data_ptr(), n1, None, B, clip_index=index, set_clips=per)
+                self._launch(0, rows, int(rows.shape[1]), act1.data_ptr(), n1, None, B, clip_index=index, set_clips=per)
             else:
-                self.fwd[0].run(slots0, n_slots0, w[1], act1.data_ptr(), n1, None, B, set_clips=per)
+                self._launch(0, slots0, n_slots0, act1.data_ptr(), n1, None, B, set_clips=per)
         else:
             for s in range(G):
                 if rows is not None:
-                    self.fwd[0].run(rows, int(rows.shape[1]), w[1], act1.data_ptr() + s * per * per1 * 16, n1, None, per,
-                                    clip_index=index[s * per:], group=s)
+                    self._launch(0, rows, int(rows.shape[1]), act1.data_ptr() + s * per * per1 * 16, n1, None, per,
+                                 clip_index=index[s * per:], group=s)
                 else:
-                    self.fwd[0].run(slots0[:, s * per * per0:], n_slots0, w[1], act1.data_ptr() + s * per * per1 * 16, n1, None, per, group=s)
-        if getattr(self, "after_first_level", None) is not None:      # (distill.DMTrainer: an event behind the first level's launch)
+                    self._launch(0, slots0[:, s * per * per0:], n_slots0, act1.data_ptr() + s * per * per1 * 16, n1, None, per, group=s)
+        if self.after_first_level is not None:      # (distill.DMTrainer: an event behind the first level's launch)
             self.after_first_level()
         for li, (src, n_src, per_src, dst_ptr, n_dst, per_dst_bytes) in enumerate((
                 (act1, n1, per1, act2.data_ptr(), n2, per2 * 16), (act2, n2, per2, feats.data_ptr(), 0, self.num_feat * 4)), start=1):
-            if li == 2 and hilo:                        # hi+lo weights: one set
-                self.fwd2x.run(src, n_src, w[5], dst_ptr, 0, None, B, out_scale=self.c8_scales if self.last_c8 else None)
-            elif per % self.fwd[li].plan.ncl == 0:       # a box never spans two sets: one launch
-                self.fwd[li].run(src, n_src, w[2 * li + 1], dst_ptr, n_dst, None, B, set_clips=per,
-                                 emit_lo=(2 if self.last_c8 else 1) if (li == 1 and hilo) else 0)
+            if (li == 2 and hilo) or per % self.fwd[li].plan.ncl == 0:      # one launch: the hi+lo level has one set / a box never spans two
+                self._launch(li, src, n_src, dst_ptr, n_dst, None, B, set_clips=per)
             else:
                 for s in range(G):
-                    self.fwd[li].run(src[:, s * per * per_src:], n_src, w[2 * li + 1], dst_ptr + s * per * per_dst_bytes, n_dst, None,
-                                     per, group=s, emit_lo=(2 if self.last_c8 else 1) if (li == 1 and hilo) else 0)
+                    self._launch(li, src[:, s * per * per_src:], n_src, dst_ptr + s * per * per_dst_bytes, n_dst, None, per, group=s)
         return feats
 
     def backward(self, saved, g_feat: torch.Tensor) -> torch.Tensor:

@@ -37,6 +37,10 @@ HEADERS = (("vd_hip.h", NAME_PATTERN),
 CORESET_METHOD = {"herding": 0, "k-center": 1}      # include/vd_hip.h VD_CORESET_HERDING / VD_CORESET_KCENTER
 PREC = {"bf16": 0, "f16": 1, "bf16x3": 2, "f16x3": 3, "f16c8": 4}      # f16c8: fp16 + fp8 corrections (the real side's last level only)
 F16X3_WSHIFT = 8          # include/vd_hip.h VD_F16X3_WSHIFT: packed fp16 hi+lo weights are W x 2^8, undone in the programs' epilogues
+# include/vd_hip.h VD_PERSIST_*: VdConvParams.persist = box-walk generations (low 16 bits) | the options of single programs
+PERSIST_GENS_MASK = 0xFFFF
+PERSIST_PLAIN_K = 1 << 19       # vd_conv0_breg: the plain K loop on a frame-tile program
+PERSIST_NO_ALT = 1 << 20        # hi+lo programs: no per-chunk sign alternation of the accumulation
 
 
 class VdConvParams(ctypes.Structure):

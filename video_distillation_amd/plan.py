@@ -1226,3 +1226,48 @@ def plan_network(geo: NetGeometry, lds_budget: int = 3700, ntw: int = 1, ntw0: i
     out = {"geo": geo, "dims": dims, "fwd": fwd, "bwd": bwd}
     _PLAN_CACHE[key] = out
     return out
+
+
+def plan_last_level(dims, base: ConvPlan, mode: str, prec: str) -> ConvPlan:
+    """The LAST level's program of a single-pass engine (``prec`` "f16" / "bf16") whose last level runs in hi+lo form, from the
+    single-pass program ``base`` (``plan_network(...)["fwd"][2]``, left as it is) and ``dims`` = the network's ``layer_dims()``:
+
+    ``mode`` "x3" -- hi+lo pairs of the same 16-bit type, three MFMAs per product: named ``fwd2_hilo``;
+    ``mode`` "c8" (f16 only) -- VD_PREC_F16C8: fp16 main product, the two hi+lo correction products on the block-scaled fp8 matrix
+    instruction once per four K steps (two MFMA-equivalents per product instead of three): named ``fwd2_c8``.  ValueError where
+    the geometry has no such program (distill.HipBackend then falls back to "x3")."""
+    assert mode in ("x3", "c8"), mode
+    d2 = dims[2]
+    pl2 = base
+    if pl2.NTW == 2 and pl2.MTW == 4 and pl2.ncl % 2 == 0:
+        # The hi+lo program keeps two operand planes of its patch in LDS: with the single-pass program's boxes (two clips, 4 M
+        # tiles x 2 N tiles per wave, 2 x 58 KB) only one workgroup fits a CU.  One clip per box (4 M tiles x 1 N tile per
+        # wave, 2 x 29 KB) lets two share it: 0.74 -> 0.68 ms per 512 clips, 4.53 -> 4.27 ms per launch in the bench (same
+        # box); same K order per output, bitwise the same features.
+        try:
+            alt = plan_forward_cl("fwd2", d2[0], d2[1], d2[2], d2[3], d2[4], d2[11], feat_out=True, ntw=1, mtw_options=(4,),
+                                  step_multiple=4 if mode == "c8" else 1)
+            if alt.rows_total <= pl2.rows_total and 2 * alt.gather_table().shape[1] * 16 <= 72 * 1024:
+                pl2 = alt
+        except ValueError:
+            pass
+    if mode == "c8":
+        # POSITION TILES (plan_forward_pos): rows = (clip, frame) pairs of one output position, so that the taps outside the input
+        # grid -- half of them at 7 x 7, two thirds at 4 x 4 -- are skipped per tile; VD_C8_POS=0 keeps the row-major program,
+        # which needs the one-clip 4 x 1-tile decomposition (not every geometry has it)
+        pos = None
+        if prec == "f16" and os.environ.get("VD_C8_POS", "1") == "1":
+            try:
+                pos = plan_forward_pos("fwd2_pos", d2[0], d2[1], d2[2], d2[3], d2[4], d2[11])
+            except (ValueError, AssertionError):
+                pos = None
+        if pos is not None:
+            pl2 = pos
+        elif prec == "f16" and pl2.NTW == 1 and pl2.MTW == 4 and pl2.S % 4 == 0:
+            # (the planners' programs are shared per process: the skip table goes into a copy of the box types)
+            pl2 = with_skip_table(dataclasses.replace(pl2, types=[dataclasses.replace(t) for t in pl2.types]))
+        else:
+            geo = NetGeometry(dims[0][2], dims[0][3], dims[0][4], dims[0][0], tuple(d[1] for d in dims), tuple(d[11] for d in dims))
+            raise ValueError("last_hilo='c8' needs the f16 format and either position tiles (frames dividing 32) or the one-clip "
+                             "4 x 1-tile last-level program (geometry %s)" % (geo,))
+    return dataclasses.replace(pl2, name="fwd2_c8" if mode == "c8" else "fwd2_hilo")
